@@ -26,6 +26,12 @@ with --gather-frames. Weak scaling. Launch for N>1:
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
       --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
+A plain run sets up, warms up, times --steps steps and prints the result
+line; --dump-outputs DIR also saves the last step's outputs. Everything
+else (the chain-kernel roofline reps, the CPU baseline, the streaming leg
+and the config-3 leg) runs only with --full and is null in the JSON
+otherwise.
+
 Rank 0 prints ONE JSON line (the driver contract).
 """
 import argparse
@@ -67,6 +73,15 @@ def parse_args():
     p.add_argument("--gather-frames", action="store_true",
                    help="all-gather every raw magnitude frame instead of "
                         "the MovingAvg-averaged spectrum")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also run the secondary "
+                        "legs (chain-kernel roofline, CPU baseline, "
+                        "PCIe-fed streaming, config 3); each can still be "
+                        "dropped with its --skip-* option. Off by default: "
+                        "a plain run measures the headline figure only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last step "
+                        "produced to DIR/<name>.npy (float32)")
     p.add_argument("--skip-cpu-baseline", action="store_true")
     p.add_argument("--skip-streaming", action="store_true",
                    help="skip the PCIe-fed ring streaming leg")
@@ -98,6 +113,38 @@ def alloc_dev(lib, bytes_):
     if lib.fsdr_dev_alloc(ctypes.byref(p), bytes_) != 0:
         raise RuntimeError(lib.fsdr_last_error().decode())
     return p
+
+
+DUMP_SAMPLE = 1 << 22  # elements kept of an output larger than this
+DUMP_SEED = 0x0D5B
+
+
+def dump_outputs(out_dir, mag, prod, avg_spec, gathered):
+    """Write the last timed step's outputs as float32 .npy files: the
+    averaged spectrum the sink emitted (`avg_spec`), the per-frame |X|^2
+    the chain wrote (`mag`) and, under torch.distributed, the all-gather
+    result (`gathered`). An array of more than DUMP_SAMPLE elements is
+    reduced to DUMP_SAMPLE elements at fixed positions (seeded draw over
+    the array's length, ascending), so two builds run with the same
+    arguments write comparable files of at most 16 MiB each."""
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+
+    def sample(t, n):
+        t = t[:n]
+        if n > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(
+                0, n, DUMP_SAMPLE, dtype=np.int64))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        return t.cpu().numpy().astype(np.float32, copy=False)
+
+    outs = {"avg_spec": sample(avg_spec, avg_spec.numel()),
+            "mag": sample(mag, prod)}
+    if gathered is not None:
+        outs["gathered"] = sample(gathered, gathered.numel())
+    for name, arr in outs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+    log(f"dumped {', '.join(outs)} to {out_dir}")
 
 
 def measure_chain_roofline(fa, torch, chain, d_in, n_samples, taps1,
@@ -491,26 +538,28 @@ def main():
     value = n_gpus * S * args.steps / elapsed / 1e6  # whole-job MSample/s
 
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, mag, prod, avg_spec, gathered)
         roofline = None
-        if not args.skip_roofline:
+        if args.full and not args.skip_roofline:
             roofline = measure_chain_roofline(fa, torch, chain, d_in, S,
                                               taps1, taps2, args.decim,
                                               args.fft, args.traffic_file,
                                               mag.data_ptr(), prod)
         cpu_baseline = None
-        if n_gpus == 1 and not args.skip_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.skip_cpu_baseline:
             log("measuring CPU baseline (oracle chain, all cores)...")
             cpu_baseline = measure_cpu_baseline(taps1, taps2, args.decim,
                                                 args.fft, args.cpu_sample)
         streaming = None
-        if n_gpus == 1 and not args.skip_streaming:
+        if args.full and n_gpus == 1 and not args.skip_streaming:
             log("measuring PCIe-fed ring streaming leg...")
             streaming = measure_streaming(fa, lib, chain, taps1, taps2,
                                           args.decim, args.fft,
                                           args.streaming_chunk,
                                           args.streaming_chunks)
         config3 = None
-        if n_gpus == 1 and not args.skip_config3:
+        if args.full and n_gpus == 1 and not args.skip_config3:
             log("measuring config-3 (FM resampler chain) leg...")
             config3 = measure_config3(fa, lib, torch)
         result = {

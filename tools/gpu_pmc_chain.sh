@@ -10,6 +10,6 @@ echo "pmc rc=$?"
 python tools/rocpd_analyze.py gpurun_out/pmc_r02/*.db > gpurun_out/pmc_sq_summary.txt 2>&1
 head -40 gpurun_out/pmc_sq_summary.txt
 for cap in 4096 8192 16384 32768; do
-  FSDR_FIR_GRID_CAP=$cap timeout 180 python bench.py --steps 8 --warmup 2 --skip-cpu-baseline --skip-streaming --skip-config3 2>/dev/null | python3 -c "import json,sys; d=json.load(sys.stdin); print('cap=$cap', d['value'], d['roofline']['ms_per_launch'])"
+  FSDR_FIR_GRID_CAP=$cap timeout 180 python bench.py --steps 8 --warmup 2 --full --skip-cpu-baseline --skip-streaming --skip-config3 2>/dev/null | python3 -c "import json,sys; d=json.load(sys.stdin); print('cap=$cap', d['value'], d['roofline']['ms_per_launch'])"
 done
-FSDR_CHAIN_BLOCK512=1 timeout 180 python bench.py --steps 8 --warmup 2 --skip-cpu-baseline --skip-streaming --skip-config3 2>/dev/null | python3 -c "import json,sys; d=json.load(sys.stdin); print('block512', d['value'], d['roofline']['ms_per_launch'])"
+FSDR_CHAIN_BLOCK512=1 timeout 180 python bench.py --steps 8 --warmup 2 --full --skip-cpu-baseline --skip-streaming --skip-config3 2>/dev/null | python3 -c "import json,sys; d=json.load(sys.stdin); print('block512', d['value'], d['roofline']['ms_per_launch'])"

@@ -4,7 +4,7 @@ cd /root/repo
 mkdir -p gpurun_out
 export TMPDIR=/tmp
 timeout 420 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_fin -o kt -- \
-  python bench.py --steps 5 --warmup 2 --skip-cpu-baseline --skip-streaming \
+  python bench.py --steps 5 --warmup 2 --full --skip-cpu-baseline --skip-streaming \
   > gpurun_out/kt_fin.log 2>&1
 echo "kt rc=$?"
 python tools/rocpd_analyze.py gpurun_out/prof_fin/kt_results.db > gpurun_out/rocprof_r02_final.txt 2>&1
