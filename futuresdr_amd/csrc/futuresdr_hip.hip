@@ -2108,53 +2108,121 @@ __global__ __launch_bounds__(256) void k_fir_ccf32(
  * at the end of the processed frames — e.g. the bench's spectrum sink
  * with history == frames): the EMA recurrence is chunked over frames and
  * the per-chunk EMAs composed exactly:
- *   ema(chunk_0..c) = (1-d)^len_c * ema(chunk_0..c-1) + partial_c. */
+ *   ema(chunk_0..c) = (1-d)^len_c * ema(chunk_0..c-1) + partial_c.
+ *
+ * Only chunks [c0, n_chunks) are computed and summed: the host proves the
+ * weight om^(frames - end_c) of every earlier chunk is exactly 0.0f (see
+ * movavg_horizon), so they cannot change a bit of the result. Partial
+ * rows below c0 are never written nor read. */
+#define MOVAVG_BATCH 16 /* loads issued per thread before it waits */
+
+/* One EMA step. The loops used to say `om*p + decay*t` and leave the
+ * rounding to the compiler's contraction, which chose differently in
+ * the two shapes (read off the gfx950 ISA of the previous build): the
+ * float4 loop was v_pk_mul + v_pk_fma, i.e. fma(decay, t, round(om*p)),
+ * the scalar loop v_pk_mul + v_add, i.e. round(om*p) + round(decay*t).
+ * Those two forms are now spelled out with contraction off, so the
+ * output stays bit-identical to that build and no longer depends on how
+ * the loop is unrolled or which compiler builds it. */
+__device__ __forceinline__ float movavg_step_v4(float p, float t, float om,
+                                                float decay) {
+#pragma clang fp contract(off)
+    const float m = om * p;
+    return isfinite(t) ? fmaf(decay, t, m) : m;
+}
+
+__device__ __forceinline__ float movavg_step_s(float p, float t, float om,
+                                               float decay) {
+#pragma clang fp contract(off)
+    const float m = om * p;
+    const float d = decay * t;
+    return isfinite(t) ? m + d : m;
+}
+
 __global__ void k_moving_avg_chunks(const float* __restrict__ in,
                                     float* __restrict__ partial, int width,
                                     long long frames, int n_chunks,
-                                    int chunk_frames, float decay) {
+                                    int chunk_frames, float decay, int c0) {
+    /* The frame loop is a serial recurrence, but its loads do not depend
+     * on it: with few live chunks the kernel is load-latency bound, so
+     * loads go out MOVAVG_BATCH at a time ahead of the dependent
+     * multiply-adds. The per-bin operation order is that of the plain
+     * loop. */
+    const float om = 1.0f - decay;
     /* width % 4 == 0 fast shape: one float4 of bins per thread */
     if ((width & 3) == 0) {
         int w4 = width >> 2;
         long long id = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-        long long total = (long long)n_chunks * w4;
+        long long total = (long long)(n_chunks - c0) * w4;
         long long stride = (long long)gridDim.x * blockDim.x;
         for (; id < total; id += stride) {
-            int c = (int)(id / w4);
-            int b4 = (int)(id - (long long)c * w4);
+            int lc = (int)(id / w4);
+            int b4 = (int)(id - (long long)lc * w4);
+            int c = c0 + lc;
             long long f0 = (long long)c * chunk_frames;
             long long f1 = f0 + chunk_frames;
             if (f1 > frames) f1 = frames;
             float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-            const float om = 1.0f - decay;
-            for (long long f = f0; f < f1; f++) {
+            long long f = f0;
+            for (; f + MOVAVG_BATCH <= f1; f += MOVAVG_BATCH) {
+                v4f t[MOVAVG_BATCH];
+#pragma unroll
+                for (int u = 0; u < MOVAVG_BATCH; u++)
+                    t[u] = *(const v4f*)&in[(f + u) * width + 4 * b4];
+                /* left alone, the compiler sinks each load to its use to
+                 * save registers and 2-3 stay in flight (a sched_barrier
+                 * here does not hold them either): passing the whole
+                 * batch through an empty asm makes it issue every load
+                 * first; it then waits once per batch, not per frame */
+                static_assert(MOVAVG_BATCH == 16, "operand list below");
+                asm volatile(""
+                             : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]), "+v"(t[3]),
+                               "+v"(t[4]), "+v"(t[5]), "+v"(t[6]), "+v"(t[7]),
+                               "+v"(t[8]), "+v"(t[9]), "+v"(t[10]),
+                               "+v"(t[11]), "+v"(t[12]), "+v"(t[13]),
+                               "+v"(t[14]), "+v"(t[15]));
+#pragma unroll
+                for (int u = 0; u < MOVAVG_BATCH; u++) {
+                    p.x = movavg_step_v4(p.x, t[u].x, om, decay);
+                    p.y = movavg_step_v4(p.y, t[u].y, om, decay);
+                    p.z = movavg_step_v4(p.z, t[u].z, om, decay);
+                    p.w = movavg_step_v4(p.w, t[u].w, om, decay);
+                }
+            }
+            for (; f < f1; f++) {
                 float4 t = *(const float4*)&in[f * width + 4 * b4];
-                p.x = isfinite(t.x) ? om * p.x + decay * t.x : om * p.x;
-                p.y = isfinite(t.y) ? om * p.y + decay * t.y : om * p.y;
-                p.z = isfinite(t.z) ? om * p.z + decay * t.z : om * p.z;
-                p.w = isfinite(t.w) ? om * p.w + decay * t.w : om * p.w;
+                p.x = movavg_step_v4(p.x, t.x, om, decay);
+                p.y = movavg_step_v4(p.y, t.y, om, decay);
+                p.z = movavg_step_v4(p.z, t.z, om, decay);
+                p.w = movavg_step_v4(p.w, t.w, om, decay);
             }
             *(float4*)&partial[(long long)c * width + 4 * b4] = p;
         }
         return;
     }
     long long id = blockIdx.x * (long long)blockDim.x + threadIdx.x;
-    long long total = (long long)n_chunks * width;
+    long long total = (long long)(n_chunks - c0) * width;
     long long stride = (long long)gridDim.x * blockDim.x;
     for (; id < total; id += stride) {
-        int c = (int)(id / width);
-        int b = (int)(id - (long long)c * width);
+        int lc = (int)(id / width);
+        int b = (int)(id - (long long)lc * width);
+        int c = c0 + lc;
         long long f0 = (long long)c * chunk_frames;
         long long f1 = f0 + chunk_frames;
         if (f1 > frames) f1 = frames;
         float p = 0.f;
-        for (long long f = f0; f < f1; f++) {
-            float t = in[f * width + b];
-            if (isfinite(t))
-                p = (1.0f - decay) * p + decay * t;
-            else
-                p *= 1.0f - decay;
+        long long f = f0;
+        for (; f + MOVAVG_BATCH <= f1; f += MOVAVG_BATCH) {
+            float t[MOVAVG_BATCH];
+#pragma unroll
+            for (int u = 0; u < MOVAVG_BATCH; u++)
+                t[u] = in[(f + u) * width + b];
+#pragma unroll
+            for (int u = 0; u < MOVAVG_BATCH; u++)
+                p = movavg_step_s(p, t[u], om, decay);
         }
+        for (; f < f1; f++)
+            p = movavg_step_s(p, in[f * width + b], om, decay);
         partial[(long long)c * width + b] = p;
     }
 }
@@ -2164,16 +2232,19 @@ __global__ void k_moving_avg_combine(const float* __restrict__ partial,
                                      float* __restrict__ out /* nullable */,
                                      int width, long long frames,
                                      int n_chunks, int chunk_frames,
-                                     float decay) {
+                                     float decay, int c0) {
     /* fully parallel closed form: result[b] = om^frames * avg[b] +
      * sum_c om^(frames - end_c) * partial[c][b]; one block per bin,
-     * chunks spread over lanes, LDS tree reduction. */
+     * chunks spread over lanes, LDS tree reduction. Chunks below c0
+     * carry weight 0.0f and are left out; the lane a chunk lands on
+     * does not depend on c0, so the live terms add in a fixed order. */
     __shared__ float red[256];
     const int b = blockIdx.x;
     if (b >= width) return;
     const float om = 1.0f - decay;
     float acc = 0.f;
     for (int c = threadIdx.x; c < n_chunks; c += blockDim.x) {
+        if (c < c0) continue;
         long long end = (long long)(c + 1) * chunk_frames;
         if (end > frames) end = frames;
         acc += powf(om, (float)(frames - end)) *
@@ -3471,6 +3542,88 @@ static int grid_for(long long work_items, int block) {
     return (int)g;
 }
 
+/* Frame horizon of the MovingAvg EMA: the smallest H with |om|^H < 2^-160,
+ * om = 1 - decay as the kernels form it (in float). A chunk that ends k
+ * frames before the emission is weighted by powf(om, k) in
+ * k_moving_avg_combine. 2^-160 is 2^10 times below half the smallest fp32
+ * denormal (2^-150), so for every k >= H the exact power rounds to zero
+ * with a margin no last-ulp error of powf (nor the float rounding of k
+ * above 2^24) comes near: the device weight is exactly +-0.0f. The chunk
+ * partials are finite (decay is held to [0,1] at create, so they are
+ * convex combinations of finite inputs, non-finite ones being filtered),
+ * so such a term is +-0 and adding it changes no
+ * bit of the sum: skipping it is exact, not approximate. Returns 0 when
+ * there is no horizon (|om| >= 1, or decay not a number). */
+static long long movavg_horizon(float decay) {
+    const double om = fabs((double)(1.0f - decay));
+    if (om == 0.0) return 1;
+    if (!(om < 1.0)) return 0;
+    const double h = ceil(160.0 * M_LN2 / -log(om));
+    if (!(h < 9.0e18)) return 0;
+    return h < 1.0 ? 1 : (long long)h;
+}
+
+/* MovingAvg frame accounting, equal to running
+ *   while (cons < in_frames && prod < out_frames) {
+ *       if (++i == history) { i = 0; prod++; }
+ *       cons++;
+ *   }
+ * from cons = prod = 0 and 0 <= *i < history: the first emission comes
+ * after history - i frames, then one every history frames, and the loop
+ * stops on the frame of the out_frames-th emission. */
+static void movavg_count(size_t in_frames, size_t out_frames, size_t history,
+                         size_t* cons, size_t* prod, size_t* i) {
+    *cons = *prod = 0;
+    if (out_frames == 0 || in_frames == 0) return;
+    const size_t first = history - *i;
+    size_t need = SIZE_MAX; /* frames up to the last emission, saturated */
+    if (out_frames - 1 <= (SIZE_MAX - first) / history)
+        need = first + (out_frames - 1) * history;
+    const size_t c = in_frames < need ? in_frames : need;
+    *cons = c;
+    if (c < first) {
+        *i += c;
+    } else {
+        *prod = 1 + (c - first) / history;
+        *i = (c - first) % history;
+    }
+}
+
+/* Chunking of the MovingAvg single-emission fast path over `frames` (> 0)
+ * frames, and the first chunk that can still weigh in: chunk c ends at
+ * min((c+1)*cf, frames) and counts iff frames - end_c < H, i.e.
+ * (c+1)*cf > frames - H. The last chunk ends at frames, so the result is
+ * at most nch-1. */
+static int movavg_plan(size_t frames, float decay, bool skip, int* cf_out,
+                       int* nch_out) {
+    int cf = 64; /* measured best (16 and 256 both slower) */
+    int nch = (int)((frames + cf - 1) / cf);
+    if (nch > 1024) { nch = 1024; cf = (int)((frames + nch - 1) / nch); }
+    *cf_out = cf;
+    *nch_out = nch;
+    int c0 = 0;
+    const long long H = movavg_horizon(decay);
+    if (skip && H > 0 && (long long)frames > H) {
+        c0 = (int)(((long long)frames - H) / cf);
+        if (c0 > nch - 1) c0 = nch - 1;
+    }
+    return c0;
+}
+
+extern "C" void fsdr_moving_avg_count(size_t in_frames, size_t out_frames,
+                                      size_t history, size_t* i_state,
+                                      size_t* consumed, size_t* produced) {
+    movavg_count(in_frames, out_frames, history, consumed, produced,
+                 i_state);
+}
+
+extern "C" int fsdr_moving_avg_plan(size_t frames, float decay_factor,
+                                    int skip, int* chunk_frames,
+                                    int* n_chunks) {
+    return movavg_plan(frames, decay_factor, skip != 0, chunk_frames,
+                       n_chunks);
+}
+
 static int launch_fir_cf32(fsdr_filter* f, const void* d_in, void* d_out,
                            size_t n_out, size_t n_in, hipStream_t st) {
     if (n_out == 0) return FSDR_OK;
@@ -3853,14 +4006,15 @@ extern "C" int fsdr_filter_dev(fsdr_filter* f, const void* d_in, size_t n_in,
                     "(multi-output block)");
             return FSDR_ERR_INVALID;
         case K_MOVAVG: {
-            /* replicate the work() counting loop on the host */
+            /* the work() counting loop (consume a frame, emit every
+             * history-th one, stop when input or output room runs out)
+             * in closed form: the loop itself cost ~0.15 ms of host time
+             * per call at the bench's 262143 frames */
             size_t in_frames = n_in / f->width;
             size_t out_frames = n_out / f->width;
             size_t cons = 0, prod = 0, i = f->i_state;
-            while (cons < in_frames && prod < out_frames) {
-                if (++i == f->history) { i = 0; prod++; }
-                cons++;
-            }
+            movavg_count(in_frames, out_frames, f->history, &cons, &prod,
+                         &i);
             r->consumed = cons * f->width;
             r->produced = prod * f->width;
             r->status = FSDR_BOTH_SUFFICIENT;
@@ -3868,25 +4022,29 @@ extern "C" int fsdr_filter_dev(fsdr_filter* f, const void* d_in, size_t n_in,
             if (prod <= 1 &&
                 (prod == 0 || f->i_state + cons == f->history)) {
                 /* parallel fast path: chunked EMA + exact composition */
-                int cf = 64; /* measured best (16 and 256 both slower) */
-                int nch = (int)((cons + cf - 1) / cf);
-                if (nch > 1024) { nch = 1024; cf = (int)((cons + nch - 1) / nch); }
+                /* FSDR_MOVAVG_SKIP=0 computes every chunk */
+                const char* sk = getenv("FSDR_MOVAVG_SKIP");
+                int cf, nch;
+                const int c0 = movavg_plan(cons, f->decay,
+                                           !sk || atoi(sk) != 0, &cf, &nch);
                 int rc = ensure_dev(&f->d_scratch, &f->d_scratch_bytes,
                                     (size_t)nch * f->width * 4);
                 if (rc) return rc;
+                const long long live =
+                    (long long)(nch - c0) *
+                    ((f->width & 3) == 0 ? f->width / 4 : f->width);
                 hipLaunchKernelGGL(
-                    k_moving_avg_chunks,
-                    dim3(grid_for((long long)nch * f->width, 256)),
+                    k_moving_avg_chunks, dim3(grid_for(live, 256)),
                     dim3(256), 0, st, (const float*)d_in,
                     (float*)f->d_scratch, (int)f->width, (long long)cons,
-                    nch, cf, f->decay);
+                    nch, cf, f->decay, c0);
                 HIP_TRY(hipGetLastError());
                 hipLaunchKernelGGL(k_moving_avg_combine,
                                    dim3((unsigned)f->width), dim3(256), 0,
                                    st, (const float*)f->d_scratch, f->d_avg,
                                    prod ? (float*)d_out : nullptr,
                                    (int)f->width, (long long)cons, nch, cf,
-                                   f->decay);
+                                   f->decay, c0);
                 HIP_TRY(hipGetLastError());
                 f->i_state = i;
                 return FSDR_OK;

@@ -119,6 +119,17 @@ fsdr_filter* fsdr_xlating_fir_cf32_create(const float* taps, size_t n_taps,
  * EMA over width-sized f32 frames, emitting every `history` frames. */
 fsdr_filter* fsdr_moving_avg_create(size_t width, float decay_factor,
                                     size_t history);
+/* Host-side planning the MovingAvg call does, exposed for tests (no GPU
+ * required). _count: frames consumed / spectra produced / new emission
+ * phase of one work() call from phase *i_state (< history). _plan: the
+ * single-emission fast path's chunking of `frames` frames (frames per
+ * chunk, chunk count) and the first chunk inside the EMA's frame horizon
+ * (returned; 0 when skip == 0 or nothing can be skipped). */
+void fsdr_moving_avg_count(size_t in_frames, size_t out_frames,
+                           size_t history, size_t* i_state,
+                           size_t* consumed, size_t* produced);
+int fsdr_moving_avg_plan(size_t frames, float decay_factor, int skip,
+                         int* chunk_frames, int* n_chunks);
 
 /* Filter::length() — lib.rs:65-67. */
 size_t fsdr_filter_length(const fsdr_filter* f);
