@@ -95,6 +95,19 @@ def _load():
     lib.fsdr_pfb_channelizer_run_dev.restype = ctypes.c_int
     lib.fsdr_pfb_channelizer_run_dev.argtypes = [vp, vp, sz, vp, sz, vp,
                                                  ctypes.POINTER(sz)]
+    lib.fsdr_pfb_synthesizer_create.restype = vp
+    lib.fsdr_pfb_synthesizer_create.argtypes = [sz, f32p, sz]
+    lib.fsdr_pfb_synthesizer_count.restype = None
+    lib.fsdr_pfb_synthesizer_count.argtypes = [sz, sz, sz, sz, sz,
+                                               ctypes.POINTER(sz),
+                                               ctypes.POINTER(sz)]
+    lib.fsdr_pfb_synthesizer_run_length.restype = sz
+    lib.fsdr_pfb_synthesizer_run_length.argtypes = [sz, sz]
+    for fn in (lib.fsdr_pfb_synthesizer_run_dev,
+               lib.fsdr_pfb_synthesizer_stream_dev):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, sz, sz, vp, sz, vp, ctypes.POINTER(sz),
+                       ctypes.POINTER(sz)]
     lib.fsdr_xlating_fir_cf32_create.restype = vp
     lib.fsdr_xlating_fir_cf32_create.argtypes = [f32p, sz, sz,
                                                  ctypes.c_float,
@@ -482,6 +495,75 @@ class PfbChannelizer(Filter):
         finally:
             lib.fsdr_dev_free(d_in)
             lib.fsdr_dev_free(d_out)
+
+
+def pfb_synthesizer_count(num_channels, taps_per_filter, pushes,
+                          n_in_per_chan, out_cap):
+    """(consumed_per_chan, produced) of one synthesizer call — the host
+    planning of PfbSynthesizer.run/stream; needs no GPU."""
+    cons = ctypes.c_size_t()
+    prod = ctypes.c_size_t()
+    _load().fsdr_pfb_synthesizer_count(
+        num_channels, taps_per_filter, pushes, n_in_per_chan, out_cap,
+        ctypes.byref(cons), ctypes.byref(prod))
+    return cons.value, prod.value
+
+
+def pfb_synthesizer_run_length(num_channels, taps_per_filter):
+    """Steps one block of the fused synthesizer kernel owns (0: staged
+    path only). Needs no GPU."""
+    return _load().fsdr_pfb_synthesizer_run_length(num_channels,
+                                                   taps_per_filter)
+
+
+class PfbSynthesizer(Filter):
+    """PFB synthesizer — pfb/synthesizer.rs. chans is [num_channels, T]
+    (one row per channel); run() is one-shot from zero state, stream()
+    carries the windows across calls."""
+
+    def __init__(self, num_channels, taps):
+        self._taps_keep, p = _f32(taps)
+        self.n = num_channels
+        super().__init__(_load().fsdr_pfb_synthesizer_create(
+            num_channels, p, self._taps_keep.size))
+
+    def _call(self, fn, chans, out_cap):
+        lib = _load()
+        chans = np.ascontiguousarray(chans, CF32).reshape(self.n, -1)
+        t = chans.shape[1]
+        if out_cap is None:
+            out_cap = (t + 1) * self.n  # every step finds > N free slots
+        d_in = ctypes.c_void_p()
+        d_out = ctypes.c_void_p()
+        _check(lib.fsdr_dev_alloc(ctypes.byref(d_in), chans.size * 8 + 8))
+        _check(lib.fsdr_dev_alloc(ctypes.byref(d_out), out_cap * 8 + 8))
+        try:
+            if chans.size:
+                _check(lib.fsdr_memcpy_h2d(d_in, _c(chans), chans.size * 8))
+            cons = ctypes.c_size_t()
+            prod = ctypes.c_size_t()
+            _check(fn(self._h, d_in, t, t, d_out, out_cap, None,
+                      ctypes.byref(cons), ctypes.byref(prod)))
+            _check(lib.fsdr_synchronize())
+            out = np.zeros(prod.value, CF32)
+            if prod.value:
+                _check(lib.fsdr_memcpy_d2h(_c(out), d_out, prod.value * 8))
+            return out, cons.value
+        finally:
+            lib.fsdr_dev_free(d_in)
+            lib.fsdr_dev_free(d_out)
+
+    def run(self, chans, out_cap=None):
+        """Bulk one-shot over host channel rows; returns (out,
+        consumed_per_chan)."""
+        return self._call(_load().fsdr_pfb_synthesizer_run_dev, chans,
+                          out_cap)
+
+    def stream(self, chans, out_cap=None):
+        """One stateful call; returns (out, consumed_per_chan). Steps not
+        consumed must be re-presented by the caller."""
+        return self._call(_load().fsdr_pfb_synthesizer_stream_dev, chans,
+                          out_cap)
 
 
 class MovingAvg(Filter):

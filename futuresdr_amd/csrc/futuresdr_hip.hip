@@ -4,8 +4,10 @@
  *
  * Written for CDNA4 from scratch: 64-wide wavefronts, LDS-staged FIR tiles
  * with register sliding windows, SoA re/im LDS planes with a 2-dwords-per-16
- * pad (breaks the stride-16B bank pattern of the pair reads), radix-2
- * Stockham FFT in LDS. No CUDA shims, no hipify output.
+ * pad (breaks the stride-16B bank pattern of the pair reads), radix-4
+ * Stockham FFT in LDS, the PFB channelizer and the PFB synthesizer (one
+ * fused gather + in-LDS IFFT + commutator kernel). No CUDA shims, no
+ * hipify output.
  *
  * Numerical semantics follow the reference cores (cited per function); the
  * status/consumed/produced math is bit-exact, the float results are
@@ -2466,6 +2468,232 @@ __global__ void k_pfb_scatter(const float2* __restrict__ ifft,
     }
 }
 
+/* ================= PFB synthesizer ==================================== *
+ * src/blocks/pfb/synthesizer.rs:59-143. Per time step t one sample of
+ * every channel goes through an unnormalized inverse DFT,
+ *   v[t][c] = sum_m x_m[t] e^{+2 pi i m c / N},
+ * and v[t][c] is pushed into channel c's tpf-deep window; once the
+ * windows are full every step emits N outputs in channel order,
+ *   out[(t-(tpf-1))*N + c] = sum_{j<tpf} part[c][j] * v[t-j][c]
+ * (part = partition_filter_taps, utilities.rs:5-25; FirFilter applies the
+ * reversed taps to the oldest->newest window, fir.rs:76-88).
+ *
+ * In the kernels below time is relative to the call: t in [0, S) are the
+ * S steps consumed now, t in [-H, 0) the H <= tpf-1 carried frames
+ * (IFFT'd, oldest first). Steps t >= t_first emit. The tap table is
+ * transposed, partT[j*N + c], so lanes along c read it coalesced. */
+#define SYN_BLOCK 256
+#define SYN_TT 32 /* consecutive steps per lane in the staged commutator */
+
+/* staged 1/3: transposing gather in[c*stride + t] -> g[t*N + c] through
+ * a 32x32 LDS tile (reads coalesced along t, writes along c; the 33rd
+ * column makes the transposed read conflict-free). */
+__global__ __launch_bounds__(SYN_BLOCK) void k_pfb_synth_gather(
+    const float2* __restrict__ in, float2* __restrict__ g, int N,
+    long long stride, long long steps) {
+    __shared__ float2 tile[32][33];
+    const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5;
+    const long long tiles_c = (N + 31) / 32;
+    const long long tiles = tiles_c * ((steps + 31) / 32);
+    for (long long id = blockIdx.x; id < tiles; id += gridDim.x) {
+        const long long tb = (id / tiles_c) * 32;
+        const int cb = (int)(id % tiles_c) * 32;
+        for (int r = ly; r < 32; r += 8) {
+            const int c = cb + r;
+            const long long t = tb + lx;
+            if (c < N && t < steps) tile[r][lx] = in[c * stride + t];
+        }
+        __syncthreads();
+        for (int r = ly; r < 32; r += 8) {
+            const long long t = tb + r;
+            const int c = cb + lx;
+            if (c < N && t < steps) g[t * N + c] = tile[lx][r];
+        }
+        __syncthreads();
+    }
+}
+
+/* staged 3/3: commutator FIR over the IFFT'd frames v[(H+t)*N + c]. A
+ * lane owns one channel and SYN_TT consecutive steps, so the tpf frames
+ * a step reads are the ones its neighbours just pulled through L2. */
+__global__ void k_pfb_synth_comm(const float2* __restrict__ v,
+                                 float2* __restrict__ out,
+                                 const float* __restrict__ partT, int N,
+                                 int tpf, long long H, long long t_first,
+                                 long long steps_out) {
+    const long long runs = (steps_out + SYN_TT - 1) / SYN_TT;
+    const long long total = runs * N;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long id = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+         id < total; id += stride) {
+        const long long r = id / N;
+        const int c = (int)(id - r * N);
+        const long long k0 = r * SYN_TT;
+        const long long k1 = k0 + SYN_TT < steps_out ? k0 + SYN_TT
+                                                     : steps_out;
+        for (long long k = k0; k < k1; k++) {
+            const float2* vt = v + (H + t_first + k) * N + c;
+            float sre = 0.f, sim = 0.f;
+            for (int j = 0; j < tpf; j++) {
+                float2 x = vt[-(long long)j * N];
+                float tap = partT[j * N + c];
+                sre = fmaf(x.x, tap, sre);
+                sim = fmaf(x.y, tap, sim);
+            }
+            out[k * N + c] = make_float2(sre, sim);
+        }
+    }
+}
+
+/* Start-up rows. The reference's WindowBuffer::new(len, false)
+ * (window_buffer.rs:13-32) does not fill in order: fill-phase push k
+ * lands at position 2k mod tpf, so until the tpf ordinary pushes that
+ * follow have rewritten every position, the window is a shuffle of the
+ * early frames with some lost and some holes still zero. The first tpf
+ * emitted steps e = 0..tpf-1 (global step tpf-1+e) therefore differ from
+ * the steady-state formula, and this kernel rewrites them the way the
+ * reference computes them. Window position w of step e is buffer slot
+ * x = (e+w) mod tpf, which holds frame tpf+x once rewritten (x < e),
+ * else the last fill push k < tpf with 2k = x (mod tpf), else zero.
+ * ve = IFFT'd frames of global steps 0..2tpf-2. */
+__global__ void k_pfb_synth_startup(const float2* __restrict__ ve,
+                                    float2* __restrict__ out,
+                                    const float* __restrict__ partT, int N,
+                                    int tpf, int e0, int n_e) {
+    const long long total = (long long)n_e * N;
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long id = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+         id < total; id += stride) {
+        const int e = e0 + (int)(id / N), c = (int)(id % N);
+        float sre = 0.f, sim = 0.f;
+        for (int w = 0; w < tpf; w++) {
+            const int x = (e + w) % tpf;
+            int fr;
+            if (x < e) fr = tpf + x;
+            else if (((x + tpf) & 1) == 0) fr = (x + tpf) / 2;
+            else if ((x & 1) == 0) fr = x / 2;
+            else continue;
+            float2 v = ve[(long long)fr * N + c];
+            float tap = partT[(tpf - 1 - w) * N + c];
+            sre = fmaf(v.x, tap, sre);
+            sim = fmaf(v.y, tap, sim);
+        }
+        out[id] = make_float2(sre, sim);
+    }
+}
+
+/* fused: gather + IFFT + commutator in one launch, v never leaves LDS.
+ * A block owns R consecutive steps [t0, t0+R) and rebuilds the hp >=
+ * tpf-1 frames in front of them (block 0 takes them from the carried
+ * history instead). It works in passes of F >= 8 steps: every channel's
+ * F consecutive samples are one >= 64 B global read, transposed into
+ * `stage` as F frames (frame stride FS = N + 64/F float2, which spreads
+ * the 64 lanes of the transposing write over all banks). Groups of G
+ * frames then run the in-LDS FFT, G frames side by side with
+ * blockDim/G threads each, between their stage frame and a slot of the ring of
+ * M = G + tpf-1 frames; IFFT(x) = conj(FFT(conj x)), so samples are
+ * conjugated on load and the ring holds conj(v). The commutator reads
+ * the ring with lanes along c and stores whole output rows. Frames are
+ * kept fft_swz-permuted throughout. */
+template <int NL>
+__global__ __launch_bounds__(1024) void k_pfb_synth_fused(
+    const float2* __restrict__ in, long long stride, long long S,
+    const float2* __restrict__ hist_old, long long H,
+    float2* __restrict__ hist_new, long long hn_first, long long hn_keep,
+    float2* __restrict__ out, long long t_first,
+    const float* __restrict__ partT, const float2* __restrict__ twid,
+    int N, int log2n, int tpf, int F, int G, int FS, int R, int hp) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float2* stage = (float2*)smem;                /* [F][FS] */
+    float2* ring = stage + (size_t)F * FS;        /* [M][FS] */
+    const int M = G + tpf - 1;
+    const int tid = threadIdx.x;
+    const int nth = blockDim.x;    /* == F*N/NL */
+    const int tpg = nth / G;       /* threads per frame in the FFT */
+    const int fl = tid / tpg, tf = tid - fl * tpg;
+    /* a pass's F*N samples, NL per thread, held in registers from their
+     * global load until the stage is free: the next pass's loads are in
+     * flight under this pass's FFTs and commutator */
+    float2 pre[NL];
+    auto load_pass = [&](long long tb) {
+#pragma unroll
+        for (int k = 0; k < NL; k++) {
+            const int idx = tid + k * nth;
+            const int c = idx / F, f = idx - c * F;
+            const long long t = tb + f;
+            pre[k] = t < S ? in[c * stride + t] : make_float2(0.f, 0.f);
+        }
+    };
+
+    for (long long t0 = (long long)blockIdx.x * R; t0 < S;
+         t0 += (long long)gridDim.x * R) {
+        const long long tend = t0 + R < S ? t0 + R : S;
+        const long long tb0 = t0 == 0 ? 0 : t0 - hp;
+        load_pass(tb0);
+        /* ring slot of step t is (t - t0 + hp) mod M */
+        if (t0 == 0) {
+            for (int idx = tid; idx < (tpf - 1) * N; idx += nth) {
+                const int jf = idx >> log2n, c = idx & (N - 1);
+                const long long t = -(long long)(tpf - 1) + jf;
+                float2 x = make_float2(0.f, 0.f);
+                if (t >= -H) {
+                    x = hist_old[(H + t) * N + c];
+                    x.y = -x.y;
+                }
+                const int slot = (int)((t + hp) % M);
+                ring[(size_t)slot * FS + fft_swz(c)] = x;
+            }
+        }
+        for (long long tb = tb0; tb < tend; tb += F) {
+#pragma unroll
+            for (int k = 0; k < NL; k++) {
+                const int idx = tid + k * nth;
+                const int c = idx / F, f = idx - c * F;
+                stage[(size_t)f * FS + fft_swz(c)] =
+                    make_float2(pre[k].x, -pre[k].y);
+            }
+            __syncthreads();
+            if (tb + F < tend) load_pass(tb + F);
+            for (int g0 = 0; g0 < F && tb + g0 < tend; g0 += G) {
+                {
+                    const long long q = tb + g0 + fl - t0 + hp;
+                    float2* a = stage + (size_t)(g0 + fl) * FS;
+                    float2* b = ring + (size_t)(q % M) * FS;
+                    float2* res = fft_pow2_fwd(a, b, twid, N, tf, tpg);
+                    if (res == a) { /* even stage count: move to the ring */
+                        for (int i = tf; i < N; i += tpg) b[i] = a[i];
+                        __syncthreads();
+                    }
+                }
+                for (int idx = tid; idx < G * N; idx += nth) {
+                    const int gf = idx >> log2n, c = idx & (N - 1);
+                    const long long t = tb + g0 + gf;
+                    if (t < t0 || t >= tend) continue;
+                    const int s = (int)((t - t0 + hp) % M);
+                    const unsigned cs = fft_swz(c);
+                    if (hist_new && t >= hn_first) {
+                        float2 x = ring[(size_t)s * FS + cs];
+                        x.y = -x.y;
+                        hist_new[(hn_keep + t - hn_first) * N + c] = x;
+                    }
+                    if (t < t_first) continue;
+                    float sre = 0.f, sim = 0.f;
+                    int sj = s;
+                    for (int j = 0; j < tpf; j++) {
+                        float2 x = ring[(size_t)sj * FS + cs];
+                        float tap = partT[j * N + c];
+                        sre = fmaf(x.x, tap, sre);
+                        sim = fmaf(x.y, tap, sim);
+                        if (--sj < 0) sj += M;
+                    }
+                    out[(t - t_first) * N + c] = make_float2(sre, -sim);
+                }
+                __syncthreads();
+            }
+        }
+    }
+}
+
 /* ================= MovingAvg ========================================== *
  * src/blocks/moving_avg.rs:79-118: per-bin EMA over WIDTH-sized frames,
  * emit every `history` frames; avg state lives in HBM (stateful block).
@@ -3010,7 +3238,7 @@ static fsdr_filter_result resamp_status(size_t L, size_t M, size_t nt_total,
 
 enum FilterKind { K_FIR_CF32, K_FIR_F32, K_DECIM_CF32, K_RESAMP_CF32,
                   K_FFT_CF32, K_MAG2, K_FIR_CCF32, K_MOVAVG,
-                  K_XLATING, K_PFB };
+                  K_XLATING, K_PFB, K_PFB_SYNTH };
 
 struct fsdr_filter {
     FilterKind kind;
@@ -3059,6 +3287,13 @@ struct fsdr_filter {
     void* d_hist = nullptr;
     size_t d_hist_bytes = 0;
     size_t pfb_pushes = 0;
+    /* PFB synthesizer: d_taps is the transposed partition partT[j*N+c];
+     * d_hist holds two (tpf-1)*N-frame halves of IFFT'd history, the
+     * live one picked by i_state (a launch reads one and writes the
+     * other); pfb_pushes counts consumed steps; d_early keeps the
+     * IFFT'd frames of steps 0..2tpf-2 for the start-up rows. */
+    void* d_early = nullptr;
+    size_t d_early_bytes = 0;
 };
 
 static int ensure_dev(void** p, size_t* cur, size_t want) {
@@ -3477,6 +3712,128 @@ extern "C" fsdr_filter* fsdr_pfb_channelizer_create(size_t num_channels,
     return f;
 }
 
+/* ---- PFB synthesizer: host-side planning ----------------------------- */
+
+/* One work() call of synthesizer.rs:86-118 in closed form: `pushes`
+ * steps consumed so far, n steps of input, out_cap output slots. The
+ * first tpf-1 steps only fill the windows; the next (filling) step emits
+ * whatever the room (the flag is updated after the step, :115-117);
+ * every later step needs MORE than N free slots (:94). The reference
+ * indexes out of range when the filling step has fewer than N slots;
+ * here the call stops in front of that step instead. */
+static void pfb_synth_count(size_t N, size_t tpf, size_t pushes, size_t n,
+                            size_t out_cap, size_t* fill_out,
+                            size_t* steps_out) {
+    size_t fill = pushes < tpf - 1 ? std::min(tpf - 1 - pushes, n) : 0;
+    size_t rem = n - fill, steps = 0;
+    const size_t room = out_cap > N ? (out_cap - N + N - 1) / N : 0;
+    if (rem == 0) {
+        steps = 0;
+    } else if (pushes + fill == tpf - 1) {
+        if (out_cap >= N) {
+            steps = 1;
+            if (rem > 1 && out_cap > 2 * N)
+                steps += std::min(rem - 1, room - 1);
+        }
+    } else {
+        steps = std::min(rem, room);
+    }
+    *fill_out = fill;
+    *steps_out = steps;
+}
+
+extern "C" void fsdr_pfb_synthesizer_count(size_t num_channels,
+                                           size_t taps_per_filter,
+                                           size_t pushes,
+                                           size_t n_in_per_chan,
+                                           size_t out_cap,
+                                           size_t* consumed_per_chan,
+                                           size_t* produced) {
+    size_t fill = 0, steps = 0;
+    if (num_channels && taps_per_filter)
+        pfb_synth_count(num_channels, taps_per_filter, pushes,
+                        n_in_per_chan, out_cap, &fill, &steps);
+    if (consumed_per_chan) *consumed_per_chan = fill + steps;
+    if (produced) *produced = steps * num_channels;
+}
+
+/* Shape of the fused kernel for (N, tpf): F steps per pass (>= 8 so a
+ * channel's read is >= 64 B, more for small N to keep 256 threads in
+ * butterflies), G frames per FFT group (F, halved until the LDS fits),
+ * R = 32 F steps per block (halo recomputation <= (tpf-1+F)/R), hp the
+ * halo rounded up to whole passes. Returns false where the fused path
+ * stops: N > 1024, or stage + ring over the 160 KB LDS even at G = 1. */
+struct SynthPlan { int F, G, FS, R, hp, threads, NL; size_t lds; };
+static bool pfb_synth_plan(size_t N, size_t tpf, SynthPlan* pl) {
+    if (N < 4 || N > 1024 || (N & (N - 1)) || tpf == 0) return false;
+    size_t F = 2048 / N;
+    F = F < 8 ? 8 : (F > 64 ? 64 : F);
+    const size_t FS = N + 64 / F;
+    const size_t R = 32 * F;
+    const size_t hp = (tpf - 1 + F - 1) / F * F;
+    if (hp > R) return false;
+    size_t G = F;
+    while (G > 1 && (F + G + tpf - 1) * FS * 8 > 160 * 1024) G >>= 1;
+    const size_t lds = (F + G + tpf - 1) * FS * 8;
+    if (lds > 160 * 1024) return false;
+    pl->F = (int)F; pl->G = (int)G; pl->FS = (int)FS; pl->R = (int)R;
+    pl->hp = (int)hp; pl->lds = lds;
+    /* a quarter of a pass's samples, within [256, 1024]: the LDS a block
+     * holds grows with F*N, so its thread count has to as well or the CU
+     * runs out of waves to hide the loads behind */
+    size_t th = F * N / 4;
+    th = th < 256 ? 256 : (th > 1024 ? 1024 : th);
+    pl->threads = (int)th;
+    pl->NL = (int)(F * N / th);
+    return true;
+}
+
+extern "C" size_t fsdr_pfb_synthesizer_run_length(size_t num_channels,
+                                                  size_t taps_per_filter) {
+    SynthPlan pl;
+    return pfb_synth_plan(num_channels, taps_per_filter, &pl) ? pl.R : 0;
+}
+
+extern "C" fsdr_filter* fsdr_pfb_synthesizer_create(size_t num_channels,
+                                                    const float* taps,
+                                                    size_t n_taps) {
+    if (!taps) { set_err("pfb synthesizer: null taps"); return nullptr; }
+    if ((num_channels & (num_channels - 1)) != 0 || num_channels < 4 ||
+        num_channels > 4096) {
+        set_err("pfb synthesizer: num_channels must be a power of two in "
+                "[4,4096] (FFT kernel constraint)");
+        return nullptr;
+    }
+    /* utilities.rs:5-25: the zero-pad count underflows otherwise */
+    if (n_taps < num_channels) {
+        set_err("pfb synthesizer: taps.len() >= num_channels");
+        return nullptr;
+    }
+    fsdr_filter* f = create_common(K_PFB_SYNTH);
+    if (!f) return nullptr;
+    const size_t N = num_channels;
+    const size_t tpf = (n_taps + N - 1) / N;
+    f->width = N;
+    f->history = tpf;
+    f->n_taps = n_taps;
+    /* partition_filter_taps, transposed: partT[j][c] = taps[c + j*N] */
+    std::vector<float> part(N * tpf, 0.f);
+    for (size_t t = 0; t < n_taps; t++) part[t] = taps[t];
+    if (hipMalloc(&f->d_taps, part.size() * sizeof(float)) != hipSuccess ||
+        hipMemcpy(f->d_taps, part.data(), part.size() * sizeof(float),
+                  hipMemcpyHostToDevice) != hipSuccess) {
+        set_err("pfb synthesizer taps upload failed");
+        fsdr_filter_destroy(f);
+        return nullptr;
+    }
+    f->sub = fsdr_fft_cf32_create(N, 1, 0, nullptr);
+    if (!f->sub) {
+        fsdr_filter_destroy(f);
+        return nullptr;
+    }
+    return f;
+}
+
 extern "C" fsdr_filter* fsdr_moving_avg_create(size_t width,
                                                float decay_factor,
                                                size_t history) {
@@ -3529,6 +3886,7 @@ extern "C" void fsdr_filter_destroy(fsdr_filter* f) {
     if (f->d_out) (void)hipFree(f->d_out);
     if (f->d_scratch) (void)hipFree(f->d_scratch);
     if (f->d_hist) (void)hipFree(f->d_hist);
+    if (f->d_early) (void)hipFree(f->d_early);
     delete f;
 }
 
@@ -4005,6 +4363,10 @@ extern "C" int fsdr_filter_dev(fsdr_filter* f, const void* d_in, size_t n_in,
             set_err("pfb channelizer uses fsdr_pfb_channelizer_run_dev "
                     "(multi-output block)");
             return FSDR_ERR_INVALID;
+        case K_PFB_SYNTH:
+            set_err("pfb synthesizer uses fsdr_pfb_synthesizer_run_dev "
+                    "(multi-input block)");
+            return FSDR_ERR_INVALID;
         case K_MOVAVG: {
             /* the work() counting loop (consume a frame, emit every
              * history-th one, stop when input or output room runs out)
@@ -4206,6 +4568,204 @@ extern "C" int fsdr_pfb_channelizer_stream_dev(
                            (char*)f->d_scratch + (T + cons - newT) * 8,
                            newT * 8, hipMemcpyDeviceToDevice, st));
     f->pfb_pushes = p + cons;
+    return FSDR_OK;
+}
+
+/* Synthesize S consumed steps, the first `fill` of which emit nothing,
+ * in front of H carried frames; writes the frames the next call needs to
+ * hist_new (nullable). Fused single launch where pfb_synth_plan allows
+ * (FSDR_PFB_SYNTH_FUSED=0 forces the staged gather -> IFFT -> commutator
+ * path, which takes every N). */
+static int pfb_synth_main(fsdr_filter* f, const float2* d_in,
+                          size_t in_stride, size_t S, size_t fill,
+                          float2* d_out, const float2* hist_old, size_t H,
+                          float2* hist_new, hipStream_t st) {
+    const size_t N = f->width, tpf = f->history;
+    const size_t newH = std::min(tpf - 1, H + S);
+    const size_t nn = std::min(newH, S), keep = newH - nn;
+    if (hist_new && keep)
+        HIP_TRY(hipMemcpyAsync(hist_new, hist_old + (H - keep) * N,
+                               keep * N * 8, hipMemcpyDeviceToDevice, st));
+    int log2n = 0;
+    while (((size_t)1 << log2n) < N) log2n++;
+    SynthPlan pl;
+    const char* fe = getenv("FSDR_PFB_SYNTH_FUSED");
+    if ((!fe || atoi(fe) != 0) && pfb_synth_plan(N, tpf, &pl)) {
+        const long long blocks = ((long long)S + pl.R - 1) / pl.R;
+        const int grid = (int)std::min<long long>(blocks, 256 * 32);
+#define SYN_FUSED_LAUNCH(NL_)                                                \
+    do {                                                                     \
+        static bool lds_opt_in = false;                                      \
+        if (!lds_opt_in) {                                                   \
+            HIP_TRY(hipFuncSetAttribute(                                     \
+                (const void*)k_pfb_synth_fused<NL_>,                         \
+                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));    \
+            lds_opt_in = true;                                               \
+        }                                                                    \
+        hipLaunchKernelGGL(k_pfb_synth_fused<NL_>, dim3(grid),               \
+                           dim3(pl.threads), pl.lds, st, d_in,               \
+                           (long long)in_stride, (long long)S, hist_old,     \
+                           (long long)H, hist_new, (long long)(S - nn),      \
+                           (long long)keep, d_out, (long long)fill,          \
+                           (const float*)f->d_taps,                          \
+                           (const float2*)f->sub->d_twid, (int)N, log2n,     \
+                           (int)tpf, pl.F, pl.G, pl.FS, pl.R, pl.hp);        \
+    } while (0)
+        switch (pl.NL) {
+            case 1: SYN_FUSED_LAUNCH(1); break;
+            case 2: SYN_FUSED_LAUNCH(2); break;
+            case 4: SYN_FUSED_LAUNCH(4); break;
+            default: SYN_FUSED_LAUNCH(8); break;
+        }
+#undef SYN_FUSED_LAUNCH
+        HIP_TRY(hipGetLastError());
+        return FSDR_OK;
+    }
+    int rc = ensure_dev(&f->d_in, &f->d_in_bytes, S * N * 8);
+    if (rc) return rc;
+    rc = ensure_dev(&f->d_scratch, &f->d_scratch_bytes, (H + S) * N * 8);
+    if (rc) return rc;
+    float2* v = (float2*)f->d_scratch;
+    if (H)
+        HIP_TRY(hipMemcpyAsync(v, hist_old, H * N * 8,
+                               hipMemcpyDeviceToDevice, st));
+    const long long tiles =
+        (long long)((N + 31) / 32) * (long long)((S + 31) / 32);
+    hipLaunchKernelGGL(k_pfb_synth_gather,
+                       dim3((unsigned)std::min<long long>(tiles, 256 * 32)),
+                       dim3(SYN_BLOCK), 0, st, d_in, (float2*)f->d_in,
+                       (int)N, (long long)in_stride, (long long)S);
+    HIP_TRY(hipGetLastError());
+    rc = launch_fft(f->sub, f->d_in, v + H * N, S, st);
+    if (rc) return rc;
+    if (S > fill) {
+        const long long runs = ((long long)(S - fill) + SYN_TT - 1) / SYN_TT;
+        hipLaunchKernelGGL(k_pfb_synth_comm,
+                           dim3(grid_for(runs * (long long)N, 256)),
+                           dim3(256), 0, st, (const float2*)v, d_out,
+                           (const float*)f->d_taps, (int)N, (int)tpf,
+                           (long long)H, (long long)fill,
+                           (long long)(S - fill));
+        HIP_TRY(hipGetLastError());
+    }
+    if (hist_new && nn)
+        HIP_TRY(hipMemcpyAsync(hist_new + keep * N, v + (H + S - nn) * N,
+                               nn * N * 8, hipMemcpyDeviceToDevice, st));
+    return FSDR_OK;
+}
+
+/* pfb_synth_main plus, while the stream is within its first 2tpf-1
+ * steps (`p` consumed before this call), the start-up rows: the call's
+ * early columns are IFFT'd into ve[p..] (staged gather + IFFT, a few
+ * frames) and k_pfb_synth_startup rewrites the emitted rows among them. */
+static int pfb_synth_launch(fsdr_filter* f, const float2* d_in,
+                            size_t in_stride, size_t S, size_t fill,
+                            float2* d_out, const float2* hist_old, size_t H,
+                            float2* hist_new, size_t p, float2* ve,
+                            hipStream_t st) {
+    int rc = pfb_synth_main(f, d_in, in_stride, S, fill, d_out, hist_old, H,
+                            hist_new, st);
+    const size_t N = f->width, L = f->history;
+    if (rc || L == 1 || p >= 2 * L - 1) return rc;
+    const size_t eb = std::min(p + S, 2 * L - 1), ne = eb - p;
+    rc = ensure_dev(&f->d_in, &f->d_in_bytes, ne * N * 8);
+    if (rc) return rc;
+    const long long tiles =
+        (long long)((N + 31) / 32) * (long long)((ne + 31) / 32);
+    hipLaunchKernelGGL(k_pfb_synth_gather,
+                       dim3((unsigned)std::min<long long>(tiles, 256 * 32)),
+                       dim3(SYN_BLOCK), 0, st, d_in, (float2*)f->d_in,
+                       (int)N, (long long)in_stride, (long long)ne);
+    HIP_TRY(hipGetLastError());
+    rc = launch_fft(f->sub, f->d_in, ve + p * N, ne, st);
+    if (rc) return rc;
+    const size_t ga = std::max(p, L - 1); /* first emitting step here */
+    if (ga < eb) {
+        hipLaunchKernelGGL(k_pfb_synth_startup,
+                           dim3(grid_for((long long)((eb - ga) * N), 256)),
+                           dim3(256), 0, st, (const float2*)ve,
+                           d_out + (ga - p - fill) * N,
+                           (const float*)f->d_taps, (int)N, (int)L,
+                           (int)(ga - (L - 1)), (int)(eb - ga));
+        HIP_TRY(hipGetLastError());
+    }
+    return FSDR_OK;
+}
+
+extern "C" int fsdr_pfb_synthesizer_run_dev(fsdr_filter* f,
+                                            const void* d_in,
+                                            size_t in_stride,
+                                            size_t n_in_per_chan,
+                                            void* d_out, size_t out_cap,
+                                            void* stream,
+                                            size_t* consumed_per_chan,
+                                            size_t* produced) {
+    REQUIRE_GPU();
+    if (!f || f->kind != K_PFB_SYNTH) {
+        set_err("not a pfb synthesizer");
+        return FSDR_ERR_INVALID;
+    }
+    if (n_in_per_chan > in_stride) {
+        set_err("pfb synthesizer: n_in_per_chan exceeds in_stride");
+        return FSDR_ERR_INVALID;
+    }
+    size_t fill, steps;
+    pfb_synth_count(f->width, f->history, 0, n_in_per_chan, out_cap, &fill,
+                    &steps);
+    if (consumed_per_chan) *consumed_per_chan = fill + steps;
+    if (produced) *produced = steps * f->width;
+    if (steps == 0) return FSDR_OK; /* zero state: nothing to carry */
+    int rc = ensure_dev(&f->d_out, &f->d_out_bytes,
+                        2 * f->history * f->width * 8);
+    if (rc) return rc;
+    return pfb_synth_launch(f, (const float2*)d_in, in_stride, fill + steps,
+                            fill, (float2*)d_out, nullptr, 0, nullptr, 0,
+                            (float2*)f->d_out, (hipStream_t)stream);
+}
+
+/* Streaming synthesizer: carries the last tpf-1 IFFT'd frames (the
+ * window contents) and the push count across calls, so any chunking
+ * reproduces the one-shot stream. Unconsumed steps stay with the caller,
+ * as with the channelizer. All work is enqueued on `stream`; use one
+ * stream per filter. */
+extern "C" int fsdr_pfb_synthesizer_stream_dev(fsdr_filter* f,
+                                               const void* d_in,
+                                               size_t in_stride,
+                                               size_t n_in_per_chan,
+                                               void* d_out, size_t out_cap,
+                                               void* stream,
+                                               size_t* consumed_per_chan,
+                                               size_t* produced) {
+    REQUIRE_GPU();
+    if (!f || f->kind != K_PFB_SYNTH) {
+        set_err("not a pfb synthesizer");
+        return FSDR_ERR_INVALID;
+    }
+    if (n_in_per_chan > in_stride) {
+        set_err("pfb synthesizer: n_in_per_chan exceeds in_stride");
+        return FSDR_ERR_INVALID;
+    }
+    const size_t N = f->width, tpf = f->history, p = f->pfb_pushes;
+    size_t fill, steps;
+    pfb_synth_count(N, tpf, p, n_in_per_chan, out_cap, &fill, &steps);
+    const size_t S = fill + steps;
+    if (consumed_per_chan) *consumed_per_chan = S;
+    if (produced) *produced = steps * N;
+    if (S == 0) return FSDR_OK;
+    const size_t half = (tpf - 1) * N;
+    int rc = ensure_dev(&f->d_hist, &f->d_hist_bytes, 2 * half * 8 + 8);
+    if (rc) return rc;
+    rc = ensure_dev(&f->d_early, &f->d_early_bytes, 2 * tpf * N * 8);
+    if (rc) return rc;
+    float2* h_old = (float2*)f->d_hist + f->i_state * half;
+    float2* h_new = (float2*)f->d_hist + (1 - f->i_state) * half;
+    rc = pfb_synth_launch(f, (const float2*)d_in, in_stride, S, fill,
+                          (float2*)d_out, h_old, std::min(p, tpf - 1),
+                          tpf > 1 ? h_new : nullptr, p, (float2*)f->d_early,
+                          (hipStream_t)stream);
+    if (rc) return rc;
+    f->i_state = 1 - f->i_state;
+    f->pfb_pushes = p + S;
     return FSDR_OK;
 }
 

@@ -186,6 +186,48 @@ int fsdr_pfb_channelizer_stream_dev(fsdr_filter* f, const void* d_chunk,
                                     size_t* produced_per_chan,
                                     size_t* consumed);
 
+/* PfbSynthesizer (src/blocks/pfb/synthesizer.rs:59-143): recombines
+ * num_channels Complex32 channel streams into one stream at N times the
+ * channel rate — per step an unnormalized inverse DFT across the
+ * channels, then each output phase c through its polyphase filter
+ * part[c][j] = taps[c + j*N] (tpf = ceil(n_taps/N) taps). num_channels
+ * must be a power of two in [4,4096] (FFT kernel) and n_taps >=
+ * num_channels (the reference's pad count underflows otherwise); a
+ * violation returns NULL with an error string.
+ * Input is channel-major, in[c*in_stride + t], n_in_per_chan <= in_stride
+ * steps per channel — the layout fsdr_pfb_channelizer_* writes with
+ * out_cap_per_chan as the stride. Output is the interleaved stream: the
+ * first tpf-1 steps of a stream only fill the windows, every later step
+ * emits N samples. consumed/produced follow the reference work() loop
+ * (a step past the filling one runs only while MORE than N output slots
+ * are free); _count is that arithmetic alone, host-only, for a handle
+ * that has consumed `pushes` steps so far. One deviation: where the
+ * reference would index out of range (the filling step with fewer than N
+ * free slots), the call stops in front of that step and returns FSDR_OK.
+ * run_dev = bulk from zero state, leaves the streaming state alone;
+ * stream_dev carries the window contents and the push count across
+ * calls, and the caller re-presents unconsumed steps. All work is
+ * enqueued on `stream` without a host sync. _run_length: steps one block
+ * of the fused kernel owns for (num_channels, taps_per_filter), 0 where
+ * only the staged path applies (diagnostics/tests; host-only). */
+fsdr_filter* fsdr_pfb_synthesizer_create(size_t num_channels,
+                                         const float* taps, size_t n_taps);
+void fsdr_pfb_synthesizer_count(size_t num_channels, size_t taps_per_filter,
+                                size_t pushes, size_t n_in_per_chan,
+                                size_t out_cap, size_t* consumed_per_chan,
+                                size_t* produced);
+size_t fsdr_pfb_synthesizer_run_length(size_t num_channels,
+                                       size_t taps_per_filter);
+int fsdr_pfb_synthesizer_run_dev(fsdr_filter* f, const void* d_in,
+                                 size_t in_stride, size_t n_in_per_chan,
+                                 void* d_out, size_t out_cap, void* stream,
+                                 size_t* consumed_per_chan, size_t* produced);
+int fsdr_pfb_synthesizer_stream_dev(fsdr_filter* f, const void* d_in,
+                                    size_t in_stride, size_t n_in_per_chan,
+                                    void* d_out, size_t out_cap,
+                                    void* stream, size_t* consumed_per_chan,
+                                    size_t* produced);
+
 /* WLAN sync-short autocorrelation helpers (examples/wlan/src/bin/
  * rx.rs:73-96): a*conj(b) Combine and the sliding-SUM MovingAverage
  * (moving_average.rs:65-105; one-shot: len-1 zero items then sums). */

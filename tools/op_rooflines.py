@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Standalone rooflines for the off-metric-path kernels (VERDICT weak-3):
 XlatingFir (tiled), FirCC (WLAN correlator shape + bulk), resampler
-shapes, and the standalone FFT kernel. Prints TF/s or GB/s vs peak."""
+shapes, the standalone FFT kernel, and the PFB synthesizer (fused and
+staged path per shape, plus the channelizer at the same shape for
+context). Prints TF/s or GB/s vs peak. --synth runs the PFB part only."""
 import ctypes
 import os
 import sys
@@ -31,6 +33,52 @@ def timeit(fn, reps=10, warm=3):
     return e0.elapsed_time(e1) / reps
 
 
+def pfb_synth_lines(lib, st, d_in, d_out, S, rounds=5):
+    """Synthesizer at N in {16, 256, 1024}, tpf = 8, ~S output samples:
+    `rounds` interleaved timings of the fused and the staged path
+    (FSDR_PFB_SYNTH_FUSED is read per call), median and range of each,
+    and the achieved share of HBM peak at the op's floor of 16 B per
+    output sample (8 in, 8 out)."""
+    sz = ctypes.c_size_t
+    for N in (16, 256, 1024):
+        tpf = 8
+        taps = fa.lowpass_kaiser_n(N * tpf, 8.0, 0.5 / N)
+        syn = fa.PfbSynthesizer(N, taps)
+        T = S // N
+        cons, prod = sz(), sz()
+
+        def run():
+            rc = lib.fsdr_pfb_synthesizer_run_dev(
+                syn._h, d_in, T, T, d_out, S, ctypes.c_void_p(st.cuda_stream),
+                ctypes.byref(cons), ctypes.byref(prod))
+            assert rc == 0, lib.fsdr_last_error().decode()
+
+        ms = {"fused": [], "staged": []}
+        for _ in range(rounds):
+            for name, knob in (("fused", "1"), ("staged", "0")):
+                os.environ["FSDR_PFB_SYNTH_FUSED"] = knob
+                ms[name].append(timeit(run, reps=5, warm=2))
+        os.environ.pop("FSDR_PFB_SYNTH_FUSED", None)
+        assert cons.value == T and prod.value == (T - tpf + 1) * N
+        for name in ("fused", "staged"):
+            v = sorted(ms[name])
+            med = v[len(v) // 2]
+            tbs = prod.value * 16 / (med * 1e-3) / 1e12
+            print(f"pfb_synth(N={N},tpf={tpf}) {name:6s}: {med:7.3f} ms "
+                  f"median of {rounds} [{v[0]:.3f}..{v[-1]:.3f}]  "
+                  f"{tbs:5.2f} TB/s at 16 B/sample "
+                  f"({tbs / PEAK_HBM:.3f} of HBM peak)")
+        chz = fa.PfbChannelizer(N, taps)
+        ppc = sz()
+        v = sorted(timeit(lambda: lib.fsdr_pfb_channelizer_run_dev(
+            chz._h, d_in, S, d_out, T, ctypes.c_void_p(st.cuda_stream),
+            ctypes.byref(ppc)), reps=5, warm=2) for _ in range(rounds))
+        tbs = ppc.value * N * 16 / (v[len(v) // 2] * 1e-3) / 1e12
+        print(f"pfb_channelizer(N={N},taps={N * tpf}) context: "
+              f"{v[len(v) // 2]:7.3f} ms median [{v[0]:.3f}..{v[-1]:.3f}]  "
+              f"{tbs:5.2f} TB/s at 16 B/sample")
+
+
 def main():
     lib = fa.lib()
     fa.set_device(0)
@@ -41,6 +89,12 @@ def main():
     assert lib.fsdr_dev_alloc(ctypes.byref(d_in), S * 8) == 0
     assert lib.fsdr_dev_alloc(ctypes.byref(d_out), S * 8) == 0
     fa.fill_uniform_dev(d_in.value, S, seed=5, stream=st.cuda_stream)
+
+    if "--synth" in sys.argv[1:]:
+        pfb_synth_lines(lib, st, d_in, d_out, S)
+        lib.fsdr_dev_free(d_in)
+        lib.fsdr_dev_free(d_out)
+        return
 
     # XlatingFir: 127 taps, decim 4 (the FM front-end shape)
     taps = fa.lowpass_kaiser_n(127, fa.kaiser_beta(1e-4), 0.1)
@@ -74,6 +128,8 @@ def main():
     tf = flops / (ms * 1e-3) / 1e12
     print(f"fft_stockham(1024) bulk:   {ms:7.3f} ms  {tbs:6.2f} TB/s HBM "
           f"({tbs / PEAK_HBM:.3f} of peak), {tf:5.1f} TF/s")
+
+    pfb_synth_lines(lib, st, d_in, d_out, S)
 
     lib.fsdr_dev_free(d_in)
     lib.fsdr_dev_free(d_out)
