@@ -115,6 +115,11 @@ def _load():
     lib.fsdr_moving_avg_create.argtypes = [sz, ctypes.c_float, sz]
     lib.fsdr_filter_length.restype = sz
     lib.fsdr_filter_length.argtypes = [vp]
+    ip = ctypes.POINTER(ctypes.c_int)
+    lib.fsdr_filter_variant.restype = ctypes.c_int
+    lib.fsdr_filter_variant.argtypes = [vp, ip, ip, ip]
+    lib.fsdr_chain_variant.restype = ctypes.c_int
+    lib.fsdr_chain_variant.argtypes = [vp, ip]
     lib.fsdr_filter_host.restype = ctypes.c_int
     lib.fsdr_filter_host.argtypes = [vp, vp, sz, vp, sz, rp]
     lib.fsdr_filter_dev.restype = ctypes.c_int
@@ -296,6 +301,16 @@ class Filter:
     @property
     def length(self):
         return _load().fsdr_filter_length(self._h)
+
+    def variant(self):
+        """(kk_mfma, kk_mfma32, tp_tpl): the kernel instantiation this
+        handle's launches select, 0 where a family does not apply.
+        Host-only."""
+        kk, kk32, tp = ctypes.c_int(), ctypes.c_int(), ctypes.c_int()
+        _check(_load().fsdr_filter_variant(self._h, ctypes.byref(kk),
+                                           ctypes.byref(kk32),
+                                           ctypes.byref(tp)))
+        return kk.value, kk32.value, tp.value
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -595,6 +610,12 @@ class Chain:
         if getattr(self, "_h", None):
             _load().fsdr_chain_destroy(self._h)
             self._h = None
+
+    def variant(self):
+        """MFMA K of the fused filter (0: no fused filter). Host-only."""
+        kk = ctypes.c_int()
+        _check(_load().fsdr_chain_variant(self._h, ctypes.byref(kk)))
+        return kk.value
 
     def run_dev(self, d_in, n_in, d_out=0, out_cap=0, d_mag=0, mag_cap=0,
                 stream=None):

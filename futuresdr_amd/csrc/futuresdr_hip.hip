@@ -3863,6 +3863,24 @@ extern "C" size_t fsdr_filter_length(const fsdr_filter* f) {
     return f ? (f->kind == K_MAG2 ? 1 : f->n_taps) : 0;
 }
 
+/* Which kernel instantiation the handle's launches select (the
+ * precomputed template parameters; 0 = that family does not apply). A
+ * resampler reports its 1:4 sub-filter, or zeros without one. */
+extern "C" int fsdr_filter_variant(const fsdr_filter* f, int* kk_mfma,
+                                   int* kk_mfma32, int* tp_tpl) {
+    if (!f) { set_err("null filter"); return FSDR_ERR_INVALID; }
+    int kk = f->kk_mfma, kk32 = f->kk_mfma32, tp = f->tp_tpl;
+    if (f->kind == K_RESAMP_CF32) {
+        kk = f->sub ? f->sub->kk_mfma : 0;
+        kk32 = f->sub ? f->sub->kk_mfma32 : 0;
+        tp = f->sub ? f->sub->tp_tpl : 0;
+    }
+    if (kk_mfma) *kk_mfma = kk;
+    if (kk_mfma32) *kk_mfma32 = kk32;
+    if (tp_tpl) *tp_tpl = tp;
+    return FSDR_OK;
+}
+
 /* item sizes for the flowgraph driver (fsdr_fg.cpp) */
 extern "C" size_t fsdr_filter_item_sizes(const fsdr_filter* f,
                                          size_t* out_bytes) {
@@ -3898,6 +3916,17 @@ static int grid_for(long long work_items, int block) {
     if (g > cap) g = cap;
     if (g < 1) g = 1;
     return (int)g;
+}
+
+/* Block cap of a persistent-tile launch: `dflt` unless FSDR_FIR_GRID_CAP
+ * parses to a value >= 1 (tests force several tiles per block with it; a
+ * value below 1 is ignored, so it cannot launch an empty grid). */
+static long long grid_cap(long long dflt) {
+    if (const char* e = getenv("FSDR_FIR_GRID_CAP")) {
+        long long v = atoll(e);
+        if (v >= 1) return v;
+    }
+    return dflt;
 }
 
 /* Frame horizon of the MovingAvg EMA: the smallest H with |om|^H < 2^-160,
@@ -3989,8 +4018,7 @@ static int launch_fir_cf32(fsdr_filter* f, const void* d_in, void* d_out,
     /* one tile per block by default: independent blocks overlap their
      * staging latency with other blocks' compute (a per-block tile loop
      * stalls all 4 waves of the block at each staging barrier) */
-    long long cap = 256 * 16;
-    if (const char* e = getenv("FSDR_FIR_GRID_CAP")) cap = atoll(e);
+    long long cap = grid_cap(256 * 16);
     int grid = (int)std::min<long long>(tiles, cap);
     const char* mf32 = getenv("FSDR_FIR_MFMA32");
     if (f->kk_mfma && mf32 && atoi(mf32) != 0) {
@@ -3998,8 +4026,7 @@ static int launch_fir_cf32(fsdr_filter* f, const void* d_in, void* d_out,
          * uploads a separate array sized for K = T+31 */
         long long tiles32 =
             ((long long)n_out + MFIR32_TILE - 1) / MFIR32_TILE;
-        long long cap32 = 256 * 64;
-        if (const char* e = getenv("FSDR_FIR_GRID_CAP")) cap32 = atoll(e);
+        long long cap32 = grid_cap(256 * 64);
         int grid32 = (int)std::min<long long>(tiles32, cap32);
         unsigned elems32 = MFIR32_TILE + f->kk_mfma32 + 8;
         size_t lds32 = (2 * (size_t)((elems32 + 31u) & ~31u) +
@@ -4076,8 +4103,7 @@ static int launch_decim_cf32(fsdr_filter* f, const void* d_in, void* d_out,
     const char* dmf = getenv("FSDR_DECIM_MFMA");
     if (f->decim == 4 && f->kk_mfma && (!dmf || atoi(dmf) != 0)) {
         long long tiles = ((long long)n_out + MDFIR_TILE - 1) / MDFIR_TILE;
-        long long cap = 256 * 64;
-        if (const char* e = getenv("FSDR_FIR_GRID_CAP")) cap = atoll(e);
+        long long cap = grid_cap(256 * 64);
         int grid = (int)std::min<long long>(tiles, cap);
         unsigned elemsP = MDFIR_TILE + f->kk_mfma + 8;
         size_t lds = (4 * (size_t)((elemsP + 31u) & ~31u) +
@@ -4099,8 +4125,7 @@ static int launch_decim_cf32(fsdr_filter* f, const void* d_in, void* d_out,
     }
     if (f->decim == 4 && f->tp_tpl) {
         long long tiles = ((long long)n_out + DFIRT_TILE - 1) / DFIRT_TILE;
-        long long cap = 256 * 64;
-        if (const char* e = getenv("FSDR_FIR_GRID_CAP")) cap = atoll(e);
+        long long cap = grid_cap(256 * 64);
         int grid = (int)std::min<long long>(tiles, cap);
         size_t lds = (4 * (size_t)dfirt_sp(f->tp_tpl) +
                       4 * ((size_t)f->tp_tpl + 4)) * sizeof(float);
@@ -4125,7 +4150,7 @@ static int launch_decim_cf32(fsdr_filter* f, const void* d_in, void* d_out,
                      * sizeof(float);
         long long tiles =
             ((long long)n_out + DFIR_TILE_OUT - 1) / DFIR_TILE_OUT;
-        int grid = (int)std::min<long long>(tiles, 256 * 8);
+        int grid = (int)std::min<long long>(tiles, grid_cap(256 * 8));
         hipLaunchKernelGGL(k_fir_decim4_cf32, dim3(grid), dim3(DFIR_BLOCK),
                            lds, st, (const float2*)d_in, (float2*)d_out,
                            f->d_taps, f->n_taps_padded, (long long)n_out,
@@ -4156,7 +4181,7 @@ static int launch_stockham(const float2* d_in, float2* d_out,
     if (fpb > 16) fpb = 16;
     size_t lds = 2 * (size_t)fpb * n * sizeof(float2);
     long long blocks = ((long long)frames + fpb - 1) / fpb;
-    int grid = (int)std::min<long long>(blocks, 256 * 16);
+    int grid = (int)std::min<long long>(blocks, grid_cap(256 * 16));
     hipLaunchKernelGGL(k_fft_stockham, dim3(grid), dim3(256), lds, st,
                        d_in, d_out, d_mag, d_twid, n, log2n, fpb, inverse,
                        fft_shift, norm, (long long)frames);
@@ -4239,7 +4264,7 @@ extern "C" int fsdr_filter_dev(fsdr_filter* f, const void* d_in, size_t n_in,
             unsigned elems = 1024 + f->n_taps_padded - 1;
             size_t lds = (size_t)elems * sizeof(float);
             long long tiles = ((long long)r->produced + 1023) / 1024;
-            int grid = (int)std::min<long long>(tiles, 256 * 16);
+            int grid = (int)std::min<long long>(tiles, grid_cap(256 * 16));
             hipLaunchKernelGGL(k_fir_f32, dim3(grid), dim3(256), lds, st,
                                (const float*)d_in, (float*)d_out, f->d_taps,
                                f->n_taps_padded, (long long)r->produced,
@@ -4272,7 +4297,8 @@ extern "C" int fsdr_filter_dev(fsdr_filter* f, const void* d_in, size_t n_in,
             if (lds_t <= 64 * 1024 && (!rt || atoi(rt) != 0)) {
                 long long tiles =
                     ((long long)r->produced + RS_TILE - 1) / RS_TILE;
-                int grid = (int)std::min<long long>(tiles, 256 * 64);
+                int grid =
+                    (int)std::min<long long>(tiles, grid_cap(256 * 64));
                 hipLaunchKernelGGL(k_resamp_tiled_cf32, dim3(grid),
                                    dim3(RS_BLOCK), lds_t, st,
                                    (const float2*)d_in, (float2*)d_out,
@@ -4309,7 +4335,7 @@ extern "C" int fsdr_filter_dev(fsdr_filter* f, const void* d_in, size_t n_in,
             unsigned elems = 1024 + f->n_taps - 1;
             size_t lds = ((size_t)elems + f->n_taps) * sizeof(float2);
             long long tiles = ((long long)r->produced + 1023) / 1024;
-            int grid = (int)std::min<long long>(tiles, 256 * 64);
+            int grid = (int)std::min<long long>(tiles, grid_cap(256 * 64));
             hipLaunchKernelGGL(k_fir_ccf32, dim3(grid), dim3(256), lds, st,
                                (const float2*)d_in, (float2*)d_out,
                                (const float2*)f->d_taps, (int)f->n_taps,
@@ -4328,7 +4354,8 @@ extern "C" int fsdr_filter_dev(fsdr_filter* f, const void* d_in, size_t n_in,
             if (lds_t <= 64 * 1024 && (!xt || atoi(xt) != 0)) {
                 long long tiles =
                     ((long long)r->produced + XT_TILE - 1) / XT_TILE;
-                int grid = (int)std::min<long long>(tiles, 256 * 64);
+                int grid =
+                    (int)std::min<long long>(tiles, grid_cap(256 * 64));
                 hipLaunchKernelGGL(k_xlating_decim_tiled_ccf32,
                                    dim3(grid), dim3(XT_BLOCK), lds_t, st,
                                    (const float2*)d_in, (float2*)d_out,
@@ -5299,6 +5326,12 @@ extern "C" fsdr_chain* fsdr_chain_create(const float* taps1, size_t n_taps1,
     return c;
 }
 
+extern "C" int fsdr_chain_variant(const fsdr_chain* c, int* fused_kk_mfma) {
+    if (!c) { set_err("null chain"); return FSDR_ERR_INVALID; }
+    if (fused_kk_mfma) *fused_kk_mfma = c->fused ? c->fused->kk_mfma : 0;
+    return FSDR_OK;
+}
+
 extern "C" void fsdr_chain_destroy(fsdr_chain* c) {
     if (!c) return;
     fsdr_filter_destroy(c->fir1);
@@ -5341,8 +5374,8 @@ extern "C" int fsdr_chain_run_dev(fsdr_chain* c, const void* d_in,
          * decimated outputs = 1024/L frames. */
         const int KK = c->fused->kk_mfma;
         long long tiles = ((long long)prod + MDFIR_TILE - 1) / MDFIR_TILE;
-        long long cap = 8192; /* ~2 tiles/block at 2^26: best measured */
-        if (const char* e = getenv("FSDR_FIR_GRID_CAP")) cap = atoll(e);
+        /* ~2 tiles/block at 2^26: best measured */
+        long long cap = grid_cap(8192);
         int grid = (int)std::min<long long>(tiles, cap);
         unsigned elemsP = MDFIR_TILE + KK + 8;
         size_t lds = (4 * (size_t)((elemsP + 31u) & ~31u) +

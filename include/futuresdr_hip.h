@@ -134,6 +134,14 @@ int fsdr_moving_avg_plan(size_t frames, float decay_factor, int skip,
 /* Filter::length() — lib.rs:65-67. */
 size_t fsdr_filter_length(const fsdr_filter* f);
 
+/* Which kernel instantiation the handle's launches select: the MFMA K,
+ * the 32x32-MFMA K and the scalar template tap count fixed at create (0 =
+ * that family does not apply; all three 0 = the untemplated kernel). A
+ * resampler reports its 1:4 decimating sub-filter, or zeros without one.
+ * NULL out-pointers are skipped (diagnostics/tests; host-only). */
+int fsdr_filter_variant(const fsdr_filter* f, int* kk_mfma, int* kk_mfma32,
+                        int* tp_tpl);
+
 /* filter() over host spans. Stages H2D/D2H internally. */
 int fsdr_filter_host(fsdr_filter* f, const void* in, size_t n_in,
                      void* out, size_t n_out, fsdr_filter_result* r);
@@ -318,6 +326,10 @@ int fsdr_chain_run_dev(fsdr_chain* c, const void* d_in, size_t n_in,
                        void* d_out, size_t out_cap,
                        void* d_mag, size_t mag_cap,
                        void* stream, size_t* consumed, size_t* produced);
+/* MFMA K of the fused (combined-taps) filter the chain kernels are
+ * instantiated for, 0 when the chain has no fused filter
+ * (diagnostics/tests; host-only). */
+int fsdr_chain_variant(const fsdr_chain* c, int* fused_kk_mfma);
 void fsdr_chain_destroy(fsdr_chain* c);
 
 /* ---- Ring (Slab-style stream buffer) ---------------------------------- *
