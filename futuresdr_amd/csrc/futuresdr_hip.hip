@@ -998,6 +998,71 @@ __global__ __launch_bounds__(MDFIR_BLOCK, MINWG) void k_decim4_fft_mfma_tpl(
     }
 }
 
+/* Staging loader of the ap and ws chain kernels: tile tl's aligned
+ * 4-sample groups q = tid + j*MDFIR_BLOCK (group q = x[4q..4q+3] past the
+ * tile base = two 16B loads) into stqa[j]/stqb[j]; samples at or past
+ * n_in_valid read as zero.
+ *
+ * Interior tiles — every sample the tile stages lies below n_in_valid, a
+ * block-uniform test — take a straight-line path: all 2*NG loads issue
+ * back to back and the consumer waits with counted vmcnt as it uses each
+ * group. The last j keeps its q < GROUPS lane predicate (exec mask only,
+ * no else-arm), so nothing past the staged range is fetched. With the
+ * per-lane guard on every group instead, its else-arm's narrow loads share
+ * destination registers with the wide ones and the compiler drains
+ * vmcnt(0) before each group: NG dependent HBM round trips per tile
+ * (profiles/chain_staging_loads.txt). Only boundary tiles pay that now. */
+template <int KKD, int NG>
+__device__ __forceinline__ void chain_stage_load(
+    const float2* __restrict__ in, long long tl, long long n_in_valid,
+    int tid, float4 (&stqa)[NG], float4 (&stqb)[NG]) {
+    constexpr unsigned GROUPS = (MDFIR_TILE + KKD + 8) + 1;
+    static_assert(NG == (GROUPS + MDFIR_BLOCK - 1) / MDFIR_BLOCK, "NG");
+    const long long qb = tl * MDFIR_TILE;
+    if ((qb + GROUPS) * 4 <= n_in_valid) {
+        const float4* p = (const float4*)(in + (qb + tid) * 4);
+#pragma unroll
+        for (int j = 0; j < NG; j++) {
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+            float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+            if ((unsigned)(j + 1) * MDFIR_BLOCK <= GROUPS ||
+                (unsigned)(tid + j * MDFIR_BLOCK) < GROUPS) {
+                a = p[2 * j * MDFIR_BLOCK];
+                b = p[2 * j * MDFIR_BLOCK + 1];
+            }
+            stqa[j] = a;
+            stqb[j] = b;
+        }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < NG; j++) {
+        unsigned q = (unsigned)(tid + j * MDFIR_BLOCK);
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (q < GROUPS) {
+            long long xq = (qb + q) * 4;
+            if (xq + 3 < n_in_valid) {
+                a = *(const float4*)&in[xq];
+                b = *(const float4*)&in[xq + 2];
+            } else {
+                float2 e0 = (xq < n_in_valid) ? in[xq]
+                                              : make_float2(0.f, 0.f);
+                float2 e1 = (xq + 1 < n_in_valid)
+                                ? in[xq + 1] : make_float2(0.f, 0.f);
+                float2 e2 = (xq + 2 < n_in_valid)
+                                ? in[xq + 2] : make_float2(0.f, 0.f);
+                float2 e3 = (xq + 3 < n_in_valid)
+                                ? in[xq + 3] : make_float2(0.f, 0.f);
+                a = make_float4(e0.x, e0.y, e1.x, e1.y);
+                b = make_float4(e2.x, e2.y, e3.x, e3.y);
+            }
+        }
+        stqa[j] = a;
+        stqb[j] = b;
+    }
+}
+
 /* All-phase staging variant (FSDR_CHAIN_ALLPHASE=1): all 4 phase planes
  * resident at once (8 planes, ~36 KB LDS -> 4 blocks/CU instead of 6),
  * ONE staging write + barrier per tile and a contiguous 160-MFMA run —
@@ -1042,33 +1107,7 @@ __global__ __launch_bounds__(MDFIR_BLOCK) void k_decim4_fft_mfma_ap_tpl(
     constexpr int NG = (GROUPS + MDFIR_BLOCK - 1) / MDFIR_BLOCK;
     float4 stqa[NG], stqb[NG];
     auto load_all = [&](long long tl) {
-        const long long qb = tl * MDFIR_TILE;
-#pragma unroll
-        for (int j = 0; j < NG; j++) {
-            unsigned q = (unsigned)(tid + j * MDFIR_BLOCK);
-            float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-            float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (q < GROUPS) {
-                long long xq = (qb + q) * 4;
-                if (xq + 3 < n_in_valid) {
-                    a = *(const float4*)&in[xq];
-                    b = *(const float4*)&in[xq + 2];
-                } else {
-                    float2 e0 = (xq < n_in_valid) ? in[xq]
-                                                  : make_float2(0.f, 0.f);
-                    float2 e1 = (xq + 1 < n_in_valid)
-                                    ? in[xq + 1] : make_float2(0.f, 0.f);
-                    float2 e2 = (xq + 2 < n_in_valid)
-                                    ? in[xq + 2] : make_float2(0.f, 0.f);
-                    float2 e3 = (xq + 3 < n_in_valid)
-                                    ? in[xq + 3] : make_float2(0.f, 0.f);
-                    a = make_float4(e0.x, e0.y, e1.x, e1.y);
-                    b = make_float4(e2.x, e2.y, e3.x, e3.y);
-                }
-            }
-            stqa[j] = a;
-            stqb[j] = b;
-        }
+        chain_stage_load<KKD, NG>(in, tl, n_in_valid, tid, stqa, stqb);
     };
     auto write_all = [&]() {
 #pragma unroll
@@ -1186,8 +1225,11 @@ __global__ __launch_bounds__(MDFIR_BLOCK) void k_decim4_fft_mfma_ap_tpl(
  * 32-cyc/SIMD instruction shadow instead of serializing after it (the
  * incremental ubench priced the serial FFT at ~1800 CU-cyc/tile). The
  * FFT runs IN-PLACE (DIF radix-4, digit-reversed output read) in a
- * dedicated 8 KB LDS strip so staging planes stay resident; ~45.6 KB
- * LDS -> 3 blocks/CU (vs the ap kernel's 4). */
+ * dedicated 8 KB LDS strip so staging planes stay resident; with the
+ * 2.7 KB twiddle table ~48.3 KB LDS at K=80 (51.4 KB at K=144) ->
+ * 3 blocks/CU (vs the ap kernel's 4). After the staging loads an
+ * iteration issues no further VMEM instruction: twiddles come from LDS
+ * and the outputs are stored ahead of the next iteration's loads. */
 __device__ __forceinline__ unsigned rev4_10(unsigned i) {
     /* reverse 5 base-4 digits of a 10-bit index */
     unsigned r = 0;
@@ -1199,8 +1241,15 @@ __device__ __forceinline__ unsigned rev4_10(unsigned i) {
     return r;
 }
 
+/* LDS twiddle table of the ws kernel: stage s (0..4) holds 256 >> 2s
+ * entries starting at ws_tw_off(s) = 0, 256, 320, 336, 340. */
+#define WS_TW_ENTRIES 341
+__host__ __device__ constexpr unsigned ws_tw_off(int s) {
+    return (1024u - (1024u >> (2 * s))) / 3u;
+}
+
 template <int KKD>
-__global__ __launch_bounds__(MDFIR_BLOCK) void k_decim4_fft_mfma_ws_tpl(
+__global__ __launch_bounds__(MDFIR_BLOCK, 3) void k_decim4_fft_mfma_ws_tpl(
     const float2* __restrict__ in, float2* __restrict__ out,
     const float* __restrict__ rtv, long long n_out, long long n_in_valid,
     const float2* __restrict__ twid /* 1024-entry forward table */,
@@ -1213,6 +1262,7 @@ __global__ __launch_bounds__(MDFIR_BLOCK) void k_decim4_fft_mfma_ws_tpl(
     float* planes = (float*)smem;            /* [8][SPm] */
     float* s_rtx = planes + 8u * SPm;        /* [4][KKD+16] */
     float2* fbuf = (float2*)(s_rtx + 4 * (KKD + 16)); /* 1024 f2, in-place */
+    float2* s_tw = fbuf + 1024;              /* [WS_TW_ENTRIES] */
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -1224,46 +1274,39 @@ __global__ __launch_bounds__(MDFIR_BLOCK) void k_decim4_fft_mfma_ws_tpl(
         int v = i / (KKD + 16), t = i % (KKD + 16);
         s_rtx[i] = (t >= 15 && t < 15 + KKD) ? rtv[v * KKD + (t - 15)] : 0.f;
     }
+    /* The FFT stages' twiddles, once per block: stage s reads
+     * twid[q << 2s], q < 256 >> 2s, kept as one compact run per stage
+     * (256+64+16+4+1 entries, stage s at ws_tw_off(s)) so a stage's reads
+     * are contiguous in LDS. A global load inside an FFT window would
+     * return in order behind the next tile's staging loads and drain them
+     * ahead of the window's barrier. */
+    for (int i = tid; i < WS_TW_ENTRIES; i += MDFIR_BLOCK) {
+        int s = (i >= 256) + (i >= 320) + (i >= 336) + (i >= 340);
+        s_tw[i] = twid[(size_t)(i - ws_tw_off(s)) << (2 * s)];
+    }
     __syncthreads();
 
     constexpr unsigned GROUPS = (MDFIR_TILE + KKD + 8) + 1;
     constexpr int NG = (GROUPS + MDFIR_BLOCK - 1) / MDFIR_BLOCK;
     float4 stqa[NG], stqb[NG];
     auto load_all = [&](long long tl) {
-        const long long qb = tl * MDFIR_TILE;
-#pragma unroll
-        for (int j = 0; j < NG; j++) {
-            unsigned q = (unsigned)(tid + j * MDFIR_BLOCK);
-            float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-            float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (q < GROUPS) {
-                long long xq = (qb + q) * 4;
-                if (xq + 3 < n_in_valid) {
-                    a = *(const float4*)&in[xq];
-                    b = *(const float4*)&in[xq + 2];
-                } else {
-                    float2 e0 = (xq < n_in_valid) ? in[xq]
-                                                  : make_float2(0.f, 0.f);
-                    float2 e1 = (xq + 1 < n_in_valid)
-                                    ? in[xq + 1] : make_float2(0.f, 0.f);
-                    float2 e2 = (xq + 2 < n_in_valid)
-                                    ? in[xq + 2] : make_float2(0.f, 0.f);
-                    float2 e3 = (xq + 3 < n_in_valid)
-                                    ? in[xq + 3] : make_float2(0.f, 0.f);
-                    a = make_float4(e0.x, e0.y, e1.x, e1.y);
-                    b = make_float4(e2.x, e2.y, e3.x, e3.y);
-                }
-            }
-            stqa[j] = a;
-            stqb[j] = b;
-        }
+        chain_stage_load<KKD, NG>(in, tl, n_in_valid, tid, stqa, stqb);
     };
     auto write_all = [&]() {
 #pragma unroll
         for (int j = 0; j < NG; j++) {
             unsigned q = (unsigned)(tid + j * MDFIR_BLOCK);
-            if (q >= GROUPS) continue;
             float4 a = stqa[j], b = stqb[j];
+            /* Use the group on every path, not only under the lane
+             * predicates below: the compiler then waits for it here, with
+             * a counted vmcnt, and knows at load_all that no staging load
+             * is pending. With the waits only inside the predicated blocks
+             * it assumed they might have been skipped and drained
+             * vmcnt(0), the output stores included, before reusing these
+             * registers for the next tile's loads. */
+            asm volatile("" ::"v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w),
+                         "v"(b.x), "v"(b.y), "v"(b.z), "v"(b.w));
+            if (q >= GROUPS) continue;
             if (q >= 1) {
                 unsigned d1 = ((q - 1) & 3u) * SUB + ((q - 1) >> 2);
                 planes[1u * SPm + d1] = a.x;
@@ -1345,7 +1388,7 @@ __global__ __launch_bounds__(MDFIR_BLOCK) void k_decim4_fft_mfma_ws_tpl(
         float2 t0 = f2_add(x0, x2), t1 = f2_sub(x0, x2);
         float2 t2 = f2_add(x1, x3), t3 = f2_sub(x1, x3);
         float2 t3r = make_float2(t3.y, -t3.x); /* -i * t3 (forward) */
-        float2 w1 = twid[(size_t)q << (2 * s)];
+        float2 w1 = s_tw[ws_tw_off(s) + q]; /* = twid[q << 2s] */
         float2 w2 = cmulf(w1, w1);
         float2 w3 = cmulf(w2, w1);
         fbuf[fft_swz(base)] = f2_add(t0, t2);
@@ -1358,6 +1401,34 @@ __global__ __launch_bounds__(MDFIR_BLOCK) void k_decim4_fft_mfma_ws_tpl(
     v4f cim = {0.f, 0.f, 0.f, 0.f};
     bool have_prev = false;
     long long prev_base = 0;
+    /* A tile's spectrum leaves the FFT strip at the end of the iteration
+     * that finishes its FFT, but is stored only in the next iteration,
+     * between write_all and load_all. VMEM retires in order and vmcnt
+     * counts loads and stores alike: stored where they are read, the
+     * stores would be younger than the staging loads in flight, and
+     * write_all's wait for the last group (vmcnt(0), the number of
+     * stores not being static) would drain them at the loop top, a store
+     * round trip per tile. Stored here they are older than those loads;
+     * write_all's unconditional waits let the compiler issue load_all
+     * behind them without a vmcnt wait, so the next wait they meet is
+     * the next loop top's (tests/test_chain_isa_cpu.py holds both).
+     * Measured: -92 us of ~3640 on the bench's chain kernel; the wait
+     * ahead of load_all alone, while it was there, cost nothing
+     * measurable (profiles/chain_staging_loads.txt). */
+    float2 held[4] = {};
+    bool have_held = false;
+    long long held_base = 0;
+    auto store_held = [&]() {
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            long long o = held_base + tid + k * MDFIR_BLOCK;
+            if (o < n_out) {
+                float2 v = held[k];
+                if (out) out[o] = v;
+                if (mag_out) mag_out[o] = v.x * v.x + v.y * v.y;
+            }
+        }
+    };
     load_all(blockIdx.x);
     for (long long tile = blockIdx.x;
          tile * (long long)MDFIR_TILE < n_out; tile += gridDim.x) {
@@ -1370,6 +1441,7 @@ __global__ __launch_bounds__(MDFIR_BLOCK) void k_decim4_fft_mfma_ws_tpl(
                 fbuf[fft_swz(pos)] = make_float2(cre[q], cim[q]);
             }
         }
+        if (have_held) store_held(); /* ahead of the staging loads */
         __syncthreads();
         if ((tile + gridDim.x) * (long long)MDFIR_TILE < n_out)
             load_all(tile + gridDim.x);
@@ -1392,20 +1464,19 @@ __global__ __launch_bounds__(MDFIR_BLOCK) void k_decim4_fft_mfma_ws_tpl(
         mfma_vloc(3, cre, cim, GH, G, true);
         if (have_prev) fft_stage(4);
         __syncthreads();
-        if (have_prev) {
-            for (int i = tid; i < 1024; i += MDFIR_BLOCK) {
-                long long o = prev_base + i;
-                if (o < n_out) {
-                    float2 v = fbuf[fft_swz(rev4_10((unsigned)i))];
-                    if (out) out[o] = v;
-                    if (mag_out) mag_out[o] = v.x * v.x + v.y * v.y;
-                }
-            }
+        if (have_prev) { /* spectrum of prev: out of the strip, held */
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                held[k] = fbuf[fft_swz(
+                    rev4_10((unsigned)(tid + k * MDFIR_BLOCK)))];
+            held_base = prev_base;
+            have_held = true;
         }
         prev_base = tile * MDFIR_TILE;
         have_prev = true;
         __syncthreads();
     }
+    if (have_held) store_held();
     /* epilogue: FFT + output of the final tile */
     if (have_prev) {
 #pragma unroll
@@ -5416,7 +5487,7 @@ extern "C" int fsdr_chain_run_dev(fsdr_chain* c, const void* d_in,
             unsigned SPm = (elemsP + 31u) & ~31u;
             size_t lds_ws = (8 * (size_t)SPm + 4 * ((size_t)KK + 16)) *
                                 sizeof(float) +
-                            1024 * sizeof(float2);
+                            (1024 + WS_TW_ENTRIES) * sizeof(float2);
 #define CHAIN_WS_CASE(KV)                                                 \
     case KV:                                                              \
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_decim4_fft_mfma_ws_tpl<KV>), \
