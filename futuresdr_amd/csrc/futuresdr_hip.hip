@@ -24,6 +24,7 @@
 #include <cstdlib>
 #include <deque>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 #include <algorithm>
 #include <cmath>
@@ -654,7 +655,17 @@ __global__ __launch_bounds__(MFIR32_BLOCK) void k_fir_mfma32_tpl(
  * (t = 4u+v => y[k] = sum_v sum_u P_v[k+u]*rtv[v][u], P_v[i] = x[3+v+4i])
  * with each phase dot-product run as the same implicit GEMM as
  * k_fir_mfma_tpl: C accumulates over all 4 phases. KKD >= ceil(T/4)+15,
- * KKD%4==0. Staging is software-pipelined across the tile loop. */
+ * KKD%4==0. Staging is software-pipelined across the tile loop.
+ *
+ * The family is built from the chain_* pieces below, each written once:
+ *   k_decim4_mfma_tpl       halves staging + store-C-rows epilogue
+ *   k_decim4_fft_mfma_tpl   halves staging + FFT epilogue (+ stagger)
+ *   k_decim4_fft_mfma2_tpl  the same at 512 threads / 2048 outputs, with
+ *                           a two-frame fft1024_block epilogue
+ *   k_decim4_fft_mfma_ap_tpl  all-phase staging + FFT epilogue
+ *   k_decim4_fft_mfma_ws_tpl  all-phase staging, FFT pipelined into the
+ *                             next tile's MFMA phases
+ *   k_mfma_ubench_tpl, k_chain_ubench_tpl  diagnostics */
 #define MDFIR_BLOCK 256
 #define MDFIR_TILE 1024 /* decimated outputs per block */
 
@@ -670,129 +681,358 @@ __device__ void fft1024_block(float2* ping, float2* pong,
                               const float2* __restrict__ twid, int tf);
 /* fft1024_block result lands in `pong` (5 swaps); read pong[fft_swz(i)] */
 
+/* LDS twiddle table of the ws kernel: stage s (0..4) holds 256 >> 2s
+ * entries starting at ws_tw_off(s) = 0, 256, 320, 336, 340. */
+#define WS_TW_ENTRIES 341
+__host__ __device__ constexpr unsigned ws_tw_off(int s) {
+    return (1024u - (1024u >> (2 * s))) / 3u;
+}
+
+/* Geometry of the family's LDS layouts, shared by the kernels (which
+ * carve their pointers from the *_rtx/ws_fbuf offsets) and the launchers
+ * (which request the *_bytes): the two cannot disagree.
+ *
+ * Each phase plane is split into 4 sub-planes by element%4 so a lane's
+ * MFMA K-walk (idx = ab+4s) becomes stride-1: one ds_read_b128 feeds 4
+ * K-steps (the b32-per-MFMA A-reads were the round-1 issue-stall,
+ * SQ_WAIT_INST_ANY 46% — profiles/pmc_r02).
+ *
+ * halves: two phases resident at a time ([re_v0, re_v1, im_v0, im_v1]) —
+ *   halves LDS vs all-phase planes, doubling resident blocks/CU;
+ *   accumulators carry across the two halves, and each half's global
+ *   loads are issued under the other half's MFMAs. The 512-thread kernel
+ *   is this layout at <KKD, 512, 2048>.
+ * ap: all 4 phases resident ([8][SPm]: re v0..3, im v0..3).
+ * ws: ap + a 1024-entry in-place FFT strip + the WS_TW_ENTRIES twiddles. */
+template <int KKD_, int BLOCK_ = MDFIR_BLOCK, int TILE_ = MDFIR_TILE>
+struct ChainGeom {
+    static_assert(KKD_ % 4 == 0, "KKD must be a multiple of 4");
+    static constexpr int KKD = KKD_, BLOCK = BLOCK_, TILE = TILE_;
+    static constexpr unsigned elemsP = TILE + KKD + 8; /* per phase plane */
+    static constexpr unsigned SPm = (elemsP + 31u) & ~31u;
+    static constexpr unsigned SUB = SPm / 4;
+    static constexpr unsigned span = 3 + 4 * elemsP; /* input elems/tile */
+    static constexpr int NL2 = (2 * elemsP + 3 + BLOCK - 1) / BLOCK;
+    static constexpr unsigned GROUPS = elemsP + 1; /* aligned 4-groups */
+    static constexpr int NG = (GROUPS + BLOCK - 1) / BLOCK;
+    static constexpr int RTW = KKD + 16; /* s_rtx row: 15 zeros + KKD + 1 */
+    /* float offsets into the dynamic LDS segment */
+    static constexpr unsigned halves_rtx = 4 * SPm;
+    static constexpr unsigned ap_rtx = 8 * SPm;
+    static constexpr unsigned ws_fbuf = ap_rtx + 4 * RTW;
+    static constexpr size_t halves_bytes =
+        (halves_rtx + 4 * RTW) * sizeof(float);
+    static constexpr size_t ap_bytes = (ap_rtx + 4 * RTW) * sizeof(float);
+    static constexpr size_t ws_bytes =
+        ws_fbuf * sizeof(float) + (1024 + WS_TW_ENTRIES) * sizeof(float2);
+};
+
+/* A thread's place in the 16x16x4 MFMA tiling. Its K-walk in a sub-plane:
+ * sub = k4 (asub), dword offset abase + s = wave*64 + 4*r16 + s —
+ * stride-1 in s, 16 B aligned at s%4==0. */
+struct chain_lane {
+    int tid, wave, r16, k4;
+    unsigned abase, asub;
+};
+template <class G>
+__device__ __forceinline__ chain_lane chain_lane_of(int tid) {
+    const int lane = tid & 63;
+    const int r16 = lane & 15, k4 = lane >> 4;
+    const int wave = tid >> 6;
+    return {tid, wave, r16, k4, (unsigned)wave * 64 + 4u * r16,
+            (unsigned)k4 * G::SUB};
+}
+
+/* s_rtx[4][KKD+16]: phase v's taps rtv[v][0..KKD) behind a 15-zero
+ * prologue (the B fragment of output row r reads at 15 + k - r). */
+template <class G>
+__device__ __forceinline__ void chain_load_taps(
+    float* s_rtx, const float* __restrict__ rtv, int tid) {
+    for (int i = tid; i < 4 * G::RTW; i += G::BLOCK) {
+        int v = i / G::RTW, t = i % G::RTW;
+        s_rtx[i] =
+            (t >= 15 && t < 15 + G::KKD) ? rtv[v * G::KKD + (t - 15)] : 0.f;
+    }
+}
+
+/* The K-walk of one phase v over its re/im planes: b128 groups [g0,g1)
+ * and, if `tail`, the non-multiple-of-4 K remainder. g0/g1 let the ws
+ * kernel split a phase across two FFT-stage windows. PRIO brackets the
+ * run with s_setprio to boost MFMA waves over the FFT/staging phases of
+ * co-resident blocks (T5); the bare-loop ubench runs without it.
+ *
+ * b128 A-reads: one ds_read_b128 pair feeds 8 MFMAs (4 K-steps x
+ * re/im), cutting the per-MFMA issue overhead (round-1 b32 reads:
+ * SQ_WAIT_INST_ANY-heavy, profiles/pmc_sq_r02.txt). One accumulator
+ * pair, re/im alternating: same-C spacing = 2 MFMA issues = 64
+ * cyc/SIMD >= the 40-cyc dependent latency, so extra accumulator
+ * pairs only cost registers (measured: dual pairs were ~3% slower,
+ * forcing 8 waves/SIMD via VGPR caps 2x slower from spills). */
+template <class G, bool PRIO = true>
+__device__ __forceinline__ void chain_mfma_phase(
+    const float* re_plane, const float* im_plane, const float* s_rtx, int v,
+    const chain_lane& ln, v4f& cre, v4f& cim, int g0 = 0,
+    int g1 = (G::KKD / 4) / 4, bool tail = true) {
+    constexpr int KKD = G::KKD;
+    const float* pre = re_plane + ln.asub;
+    const float* pim = im_plane + ln.asub;
+    const unsigned abase = ln.abase;
+    float bfrag[KKD / 4];
+#pragma unroll
+    for (int s = 0; s < KKD / 4; s++)
+        bfrag[s] = s_rtx[v * G::RTW + 15 + 4 * s + ln.k4 - ln.r16];
+    if (PRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int t = 0; t < (KKD / 4) / 4; t++) {
+        if (t < g0 || t >= g1) continue;
+        float4 ar = *(const float4*)&pre[abase + 4 * t];
+        float4 ai = *(const float4*)&pim[abase + 4 * t];
+        cre = __builtin_amdgcn_mfma_f32_16x16x4f32(ar.x, bfrag[4 * t],
+                                                   cre, 0, 0, 0);
+        cim = __builtin_amdgcn_mfma_f32_16x16x4f32(ai.x, bfrag[4 * t],
+                                                   cim, 0, 0, 0);
+        cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
+            ar.y, bfrag[4 * t + 1], cre, 0, 0, 0);
+        cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
+            ai.y, bfrag[4 * t + 1], cim, 0, 0, 0);
+        cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
+            ar.z, bfrag[4 * t + 2], cre, 0, 0, 0);
+        cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
+            ai.z, bfrag[4 * t + 2], cim, 0, 0, 0);
+        cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
+            ar.w, bfrag[4 * t + 3], cre, 0, 0, 0);
+        cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
+            ai.w, bfrag[4 * t + 3], cim, 0, 0, 0);
+    }
+    if (tail) {
+#pragma unroll
+        for (int s = (KKD / 4) & ~3; s < KKD / 4; s++) {
+            float a_re = pre[abase + s];
+            float a_im = pim[abase + s];
+            cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                a_re, bfrag[s], cre, 0, 0, 0);
+            cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
+                a_im, bfrag[s], cim, 0, 0, 0);
+        }
+    }
+    if (PRIO) __builtin_amdgcn_s_setprio(0);
+}
+
+/* -- halves staging: phases {2h, 2h+1} of a tile at a time -------------- */
+
+/* elements of phases {2h, 2h+1}: rel = 3 + 4i + 2h + vloc; samples at or
+ * past n_in_valid read as zero */
+template <class G>
+__device__ __forceinline__ void chain_load_half(
+    const float2* __restrict__ in, long long tl, int h,
+    long long n_in_valid, int tid, float2 (&stg)[G::NL2]) {
+    const long long ib = tl * G::TILE * 4;
+#pragma unroll
+    for (int j = 0; j < G::NL2; j++) {
+        unsigned idx = (unsigned)(tid + j * G::BLOCK);
+        unsigned rel = 3 + 4 * (idx >> 1) + 2 * h + (idx & 1u);
+        long long g = ib + rel;
+        stg[j] = (rel < G::span && g < n_in_valid) ? in[g]
+                                                   : make_float2(0.f, 0.f);
+    }
+}
+
+template <class G>
+__device__ __forceinline__ void chain_write_half(
+    float* planes, int tid, const float2 (&stg)[G::NL2]) {
+#pragma unroll
+    for (int j = 0; j < G::NL2; j++) {
+        unsigned idx = (unsigned)(tid + j * G::BLOCK);
+        unsigned i = idx >> 1, vloc = idx & 1u;
+        if (i < G::elemsP) {
+            unsigned d = (i & 3u) * G::SUB + (i >> 2);
+            planes[vloc * G::SPm + d] = stg[j].x;
+            planes[(2 + vloc) * G::SPm + d] = stg[j].y;
+        }
+    }
+}
+
+/* the two resident phases of half h */
+template <class G, bool PRIO = true>
+__device__ __forceinline__ void chain_mfma_half(
+    const float* planes, const float* s_rtx, int h, const chain_lane& ln,
+    v4f& cre, v4f& cim, bool tail = true) {
+#pragma unroll
+    for (int vloc = 0; vloc < 2; vloc++)
+        chain_mfma_phase<G, PRIO>(planes + (unsigned)vloc * G::SPm,
+                                  planes + (unsigned)(2 + vloc) * G::SPm,
+                                  s_rtx, 2 * h + vloc, ln, cre, cim, 0,
+                                  (G::KKD / 4) / 4, tail);
+}
+
+/* -- all-phase staging (ap, ws) ----------------------------------------- *
+ * Staging by ALIGNED 4-sample groups: group q = x[4q..4q+3] = two 16B
+ * float4 loads (x is 32B-aligned at 4q when the base pointer is
+ * 16B-aligned — host guards). Sample x[4q+w] belongs to phase v=(w+1)&3
+ * at position q (w==3) or q-1 (w<3), since P_v[i] = x[3+v+4i]. Halves
+ * the VMEM instruction count vs float2 loads — the incremental ubench
+ * showed the staging loads cost ~25 points of MFMA-pipe utilization
+ * (issue/latency interference). */
+
+/* Staging loader of the ap and ws chain kernels: tile tl's aligned
+ * 4-sample groups q = tid + j*BLOCK (group q = x[4q..4q+3] past the
+ * tile base = two 16B loads) into stqa[j]/stqb[j]; samples at or past
+ * n_in_valid read as zero.
+ *
+ * Interior tiles — every sample the tile stages lies below n_in_valid, a
+ * block-uniform test — take a straight-line path: all 2*NG loads issue
+ * back to back and the consumer waits with counted vmcnt as it uses each
+ * group. The last j keeps its q < GROUPS lane predicate (exec mask only,
+ * no else-arm), so nothing past the staged range is fetched. With the
+ * per-lane guard on every group instead, its else-arm's narrow loads share
+ * destination registers with the wide ones and the compiler drains
+ * vmcnt(0) before each group: NG dependent HBM round trips per tile
+ * (profiles/chain_staging_loads.txt). Only boundary tiles pay that now. */
+template <class G>
+__device__ __forceinline__ void chain_stage_load(
+    const float2* __restrict__ in, long long tl, long long n_in_valid,
+    int tid, float4 (&stqa)[G::NG], float4 (&stqb)[G::NG]) {
+    constexpr unsigned GROUPS = G::GROUPS;
+    constexpr int NG = G::NG;
+    const long long qb = tl * G::TILE;
+    if ((qb + GROUPS) * 4 <= n_in_valid) {
+        const float4* p = (const float4*)(in + (qb + tid) * 4);
+#pragma unroll
+        for (int j = 0; j < NG; j++) {
+            float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+            float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+            if ((unsigned)(j + 1) * G::BLOCK <= GROUPS ||
+                (unsigned)(tid + j * G::BLOCK) < GROUPS) {
+                a = p[2 * j * G::BLOCK];
+                b = p[2 * j * G::BLOCK + 1];
+            }
+            stqa[j] = a;
+            stqb[j] = b;
+        }
+        return;
+    }
+#pragma unroll
+    for (int j = 0; j < NG; j++) {
+        unsigned q = (unsigned)(tid + j * G::BLOCK);
+        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (q < GROUPS) {
+            long long xq = (qb + q) * 4;
+            if (xq + 3 < n_in_valid) {
+                a = *(const float4*)&in[xq];
+                b = *(const float4*)&in[xq + 2];
+            } else {
+                float2 e0 = (xq < n_in_valid) ? in[xq]
+                                              : make_float2(0.f, 0.f);
+                float2 e1 = (xq + 1 < n_in_valid)
+                                ? in[xq + 1] : make_float2(0.f, 0.f);
+                float2 e2 = (xq + 2 < n_in_valid)
+                                ? in[xq + 2] : make_float2(0.f, 0.f);
+                float2 e3 = (xq + 3 < n_in_valid)
+                                ? in[xq + 3] : make_float2(0.f, 0.f);
+                a = make_float4(e0.x, e0.y, e1.x, e1.y);
+                b = make_float4(e2.x, e2.y, e3.x, e3.y);
+            }
+        }
+        stqa[j] = a;
+        stqb[j] = b;
+    }
+}
+
+/* The staged groups into the 8 phase planes. PIN (ws) uses the group on
+ * every path, not only under the lane predicates below: the compiler then
+ * waits for it here, with a counted vmcnt, and knows at the next
+ * chain_stage_load that no staging load is pending. With the waits only
+ * inside the predicated blocks it assumed they might have been skipped
+ * and drained vmcnt(0), the output stores included, before reusing these
+ * registers for the next tile's loads.
+ *
+ * planes and tid come by reference, as the kernels' capturing lambdas
+ * hand them on: taken by value the compiler shares the per-group plane
+ * offsets differently and the ws kernel's instruction stream moves
+ * (tools/isa_diff.py against the build before). */
+template <class G, bool PIN>
+__device__ __forceinline__ void chain_write_all(
+    float* const& planes, const int& tid, const float4 (&stqa)[G::NG],
+    const float4 (&stqb)[G::NG]) {
+    constexpr unsigned SPm = G::SPm, SUB = G::SUB;
+#pragma unroll
+    for (int j = 0; j < G::NG; j++) {
+        unsigned q = (unsigned)(tid + j * G::BLOCK);
+        float4 a = stqa[j], b = stqb[j];
+        if (PIN)
+            asm volatile("" ::"v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w),
+                         "v"(b.x), "v"(b.y), "v"(b.z), "v"(b.w));
+        if (q >= G::GROUPS) continue;
+        if (q >= 1) { /* w=0,1,2 -> phases 1,2,3 at position q-1 */
+            unsigned d1 = ((q - 1) & 3u) * SUB + ((q - 1) >> 2);
+            planes[1u * SPm + d1] = a.x;
+            planes[5u * SPm + d1] = a.y;
+            planes[2u * SPm + d1] = a.z;
+            planes[6u * SPm + d1] = a.w;
+            planes[3u * SPm + d1] = b.x;
+            planes[7u * SPm + d1] = b.y;
+        }
+        if (q < G::elemsP) { /* w=3 -> phase 0 at position q */
+            unsigned d0 = (q & 3u) * SUB + (q >> 2);
+            planes[0u * SPm + d0] = b.z;
+            planes[4u * SPm + d0] = b.w;
+        }
+    }
+}
+
+/* -- epilogues ----------------------------------------------------------- */
+
+/* store the tile's C rows: the filter-level output y2 */
+__device__ __forceinline__ void chain_store_rows(
+    float2* __restrict__ out, long long out_base, long long n_out,
+    const chain_lane& ln, const v4f& cre, const v4f& cim) {
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        int row = ln.k4 * 4 + q;
+        long long o = out_base + (long long)ln.wave * 256 + 16 * row + ln.r16;
+        if (o < n_out) out[o] = make_float2(cre[q], cim[q]);
+    }
+}
+
+/* The FFT epilogue of the halves and ap kernels (deposit C swizzled,
+ * fft_pow2_fwd, guarded spectrum and |X|^2 stores) stays written out in
+ * both: behind one helper, in every parameter shape tried, the ap tile
+ * loop keeps its instructions but shifts its register allocation, and
+ * that loop is held to the stream that was measured (tools/isa_diff.py,
+ * profiles/chain_refactor.txt). */
+
+/* -- kernels -------------------------------------------------------------- */
+
 template <int KKD>
 __global__ __launch_bounds__(MDFIR_BLOCK) void k_decim4_mfma_tpl(
     const float2* __restrict__ in, float2* __restrict__ out,
     const float* __restrict__ rtv /* [4][KKD], rtv[v][u] = rt[4u+v] */,
     long long n_out, long long n_in_valid) {
-    static_assert(KKD % 4 == 0, "KKD must be a multiple of 4");
-    const unsigned elemsP = MDFIR_TILE + KKD + 8;     /* per phase plane */
-    const unsigned SPm = (elemsP + 31u) & ~31u;
-    /* each phase plane is split into 4 sub-planes by element%4 so a
-     * lane's MFMA K-walk (idx = ab+4s) becomes stride-1: one
-     * ds_read_b128 feeds 4 K-steps (the b32-per-MFMA A-reads were the
-     * round-1 issue-stall, SQ_WAIT_INST_ANY 46% — profiles/pmc_r02) */
-    const unsigned SUB = SPm / 4;
+    using G = ChainGeom<KKD>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    /* two phases resident at a time ([re_v0, re_v1, im_v0, im_v1]) —
-     * halves LDS vs all-phase planes, doubling resident blocks/CU;
-     * accumulators carry across the two halves, and each half's global
-     * loads are issued under the other half's MFMAs. */
-    float* planes = (float*)smem;        /* [4][SPm] */
-    float* s_rtx = planes + 4u * SPm;    /* [4][KKD+16], 15-zero prologue */
+    float* planes = (float*)smem;           /* [4][SPm] */
+    float* s_rtx = planes + G::halves_rtx;  /* [4][KKD+16] */
+    const chain_lane ln = chain_lane_of<G>(threadIdx.x);
+    const int tid = ln.tid;
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int r16 = lane & 15;
-    const int k4 = lane >> 4;
-
-    for (int i = tid; i < 4 * (KKD + 16); i += MDFIR_BLOCK) {
-        int v = i / (KKD + 16), t = i % (KKD + 16);
-        s_rtx[i] = (t >= 15 && t < 15 + KKD) ? rtv[v * KKD + (t - 15)] : 0.f;
-    }
+    chain_load_taps<G>(s_rtx, rtv, tid);
     __syncthreads();
 
-    const unsigned span = 3 + 4 * elemsP; /* input elements per tile */
-    constexpr int NL2 =
-        (2 * (MDFIR_TILE + KKD + 8) + 3 + MDFIR_BLOCK - 1) / MDFIR_BLOCK;
-    float2 stgA[NL2], stgB[NL2];
-    /* elements of phases {2h, 2h+1}: rel = 3 + 4i + 2h + vloc */
-    auto load_half = [&](long long tl, int h, float2 (&stg)[NL2]) {
-        const long long ib = tl * MDFIR_TILE * 4;
-#pragma unroll
-        for (int j = 0; j < NL2; j++) {
-            unsigned idx = (unsigned)(tid + j * MDFIR_BLOCK);
-            unsigned rel = 3 + 4 * (idx >> 1) + 2 * h + (idx & 1u);
-            long long g = ib + rel;
-            stg[j] = (rel < span && g < n_in_valid)
-                         ? in[g] : make_float2(0.f, 0.f);
-        }
+    float2 stgA[G::NL2], stgB[G::NL2];
+    auto load_half = [&](long long tl, int h, float2 (&stg)[G::NL2]) {
+        chain_load_half<G>(in, tl, h, n_in_valid, tid, stg);
     };
-    auto write_half = [&](const float2 (&stg)[NL2]) {
-#pragma unroll
-        for (int j = 0; j < NL2; j++) {
-            unsigned idx = (unsigned)(tid + j * MDFIR_BLOCK);
-            unsigned i = idx >> 1, vloc = idx & 1u;
-            if (i < elemsP) {
-                unsigned d = (i & 3u) * SUB + (i >> 2);
-                planes[vloc * SPm + d] = stg[j].x;
-                planes[(2 + vloc) * SPm + d] = stg[j].y;
-            }
-        }
+    auto write_half = [&](const float2 (&stg)[G::NL2]) {
+        chain_write_half<G>(planes, tid, stg);
     };
-    /* lane (r16,k4)'s K-walk in a sub-plane: sub = k4, dword offset
-     * wave*64 + 4*r16 + s — stride-1 in s, 16 B aligned at s%4==0 */
-    const unsigned abase = (unsigned)wave * 64 + 4u * r16;
-    const unsigned asub = (unsigned)k4 * SUB;
-    /* b128 A-reads: one ds_read_b128 pair feeds 8 MFMAs (4 K-steps x
-     * re/im), cutting the per-MFMA issue overhead (round-1 b32 reads:
-     * SQ_WAIT_INST_ANY-heavy, profiles/pmc_sq_r02.txt). One accumulator
-     * pair, re/im alternating: same-C spacing = 2 MFMA issues = 64
-     * cyc/SIMD >= the 40-cyc dependent latency, so extra accumulator
-     * pairs only cost registers (measured: dual pairs were ~3% slower,
-     * forcing 8 waves/SIMD via VGPR caps 2x slower from spills). */
     auto mfma_half = [&](int h, v4f& cre, v4f& cim) {
-#pragma unroll
-        for (int vloc = 0; vloc < 2; vloc++) {
-            const float* pre = planes + (unsigned)vloc * SPm + asub;
-            const float* pim = planes + (unsigned)(2 + vloc) * SPm + asub;
-            const int v = 2 * h + vloc;
-            float bfrag[KKD / 4];
-#pragma unroll
-            for (int s = 0; s < KKD / 4; s++)
-                bfrag[s] = s_rtx[v * (KKD + 16) + 15 + 4 * s + k4 - r16];
-            __builtin_amdgcn_s_setprio(1); /* boost MFMA waves over the
-                                              FFT/staging phases of
-                                              co-resident blocks (T5) */
-#pragma unroll
-            for (int t = 0; t < (KKD / 4) / 4; t++) {
-                float4 ar = *(const float4*)&pre[abase + 4 * t];
-                float4 ai = *(const float4*)&pim[abase + 4 * t];
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.x, bfrag[4 * t], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.x, bfrag[4 * t], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.y, bfrag[4 * t + 1], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.y, bfrag[4 * t + 1], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.z, bfrag[4 * t + 2], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.z, bfrag[4 * t + 2], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.w, bfrag[4 * t + 3], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.w, bfrag[4 * t + 3], cim, 0, 0, 0);
-            }
-#pragma unroll
-            for (int s = (KKD / 4) & ~3; s < KKD / 4; s++) {
-                float a_re = pre[abase + s];
-                float a_im = pim[abase + s];
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    a_re, bfrag[s], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    a_im, bfrag[s], cim, 0, 0, 0);
-            }
-            __builtin_amdgcn_s_setprio(0);
-        }
+        chain_mfma_half<G>(planes, s_rtx, h, ln, cre, cim);
     };
 
     load_half(blockIdx.x, 0, stgA);
     for (long long tile = blockIdx.x;
-         tile * (long long)MDFIR_TILE < n_out; tile += gridDim.x) {
-        const long long out_base = tile * MDFIR_TILE;
+         tile * (long long)G::TILE < n_out; tile += gridDim.x) {
         v4f cre = {0.f, 0.f, 0.f, 0.f};
         v4f cim = {0.f, 0.f, 0.f, 0.f};
         write_half(stgA);
@@ -802,16 +1042,10 @@ __global__ __launch_bounds__(MDFIR_BLOCK) void k_decim4_mfma_tpl(
         __syncthreads();
         write_half(stgB);
         __syncthreads();
-        if ((tile + gridDim.x) * (long long)MDFIR_TILE < n_out)
+        if ((tile + gridDim.x) * (long long)G::TILE < n_out)
             load_half(tile + gridDim.x, 0, stgA); /* under half-1 MFMAs */
         mfma_half(1, cre, cim);
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            int row = k4 * 4 + q;
-            long long o = out_base + (long long)wave * 256 + 16 * row + r16;
-            if (o < n_out)
-                out[o] = make_float2(cre[q], cim[q]);
-        }
+        chain_store_rows(out, tile * G::TILE, n_out, ln, cre, cim);
         __syncthreads();
     }
 }
@@ -829,129 +1063,34 @@ __global__ __launch_bounds__(MDFIR_BLOCK, MINWG) void k_decim4_fft_mfma_tpl(
                    staging/FFT interval overlaps the others' MFMA runs
                    (the bare MFMA loop reaches 97% of peak —
                    tools/mfma_ubench.py — so pipe idle = phase lock) */) {
-    static_assert(MDFIR_TILE == 1024, "tile == 1024 decimated outputs");
-    static_assert(KKD % 4 == 0, "KKD must be a multiple of 4");
+    using G = ChainGeom<KKD>;
     if (stagger > 0) {
         int loops = (int)(blockIdx.x & 7u) * stagger;
         for (int i = 0; i < loops; i++) __builtin_amdgcn_s_sleep(7);
     }
-    const unsigned elemsP = MDFIR_TILE + KKD + 8;     /* per phase plane */
-    const unsigned SPm = (elemsP + 31u) & ~31u;
-    /* each phase plane is split into 4 sub-planes by element%4 so a
-     * lane's MFMA K-walk (idx = ab+4s) becomes stride-1: one
-     * ds_read_b128 feeds 4 K-steps (the b32-per-MFMA A-reads were the
-     * round-1 issue-stall, SQ_WAIT_INST_ANY 46% — profiles/pmc_r02) */
-    const unsigned SUB = SPm / 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    /* two phases resident at a time ([re_v0, re_v1, im_v0, im_v1]) —
-     * halves LDS vs all-phase planes, doubling resident blocks/CU;
-     * accumulators carry across the two halves, and each half's global
-     * loads are issued under the other half's MFMAs. */
-    float* planes = (float*)smem;        /* [4][SPm] */
-    float* s_rtx = planes + 4u * SPm;    /* [4][KKD+16], 15-zero prologue */
+    float* planes = (float*)smem;           /* [4][SPm] */
+    float* s_rtx = planes + G::halves_rtx;  /* [4][KKD+16] */
+    const chain_lane ln = chain_lane_of<G>(threadIdx.x);
+    const int tid = ln.tid;
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int r16 = lane & 15;
-    const int k4 = lane >> 4;
-
-    for (int i = tid; i < 4 * (KKD + 16); i += MDFIR_BLOCK) {
-        int v = i / (KKD + 16), t = i % (KKD + 16);
-        s_rtx[i] = (t >= 15 && t < 15 + KKD) ? rtv[v * KKD + (t - 15)] : 0.f;
-    }
+    chain_load_taps<G>(s_rtx, rtv, tid);
     __syncthreads();
 
-    const unsigned span = 3 + 4 * elemsP; /* input elements per tile */
-    constexpr int NL2 =
-        (2 * (MDFIR_TILE + KKD + 8) + 3 + MDFIR_BLOCK - 1) / MDFIR_BLOCK;
-    float2 stgA[NL2], stgB[NL2];
-    /* elements of phases {2h, 2h+1}: rel = 3 + 4i + 2h + vloc */
-    auto load_half = [&](long long tl, int h, float2 (&stg)[NL2]) {
-        const long long ib = tl * MDFIR_TILE * 4;
-#pragma unroll
-        for (int j = 0; j < NL2; j++) {
-            unsigned idx = (unsigned)(tid + j * MDFIR_BLOCK);
-            unsigned rel = 3 + 4 * (idx >> 1) + 2 * h + (idx & 1u);
-            long long g = ib + rel;
-            stg[j] = (rel < span && g < n_in_valid)
-                         ? in[g] : make_float2(0.f, 0.f);
-        }
+    float2 stgA[G::NL2], stgB[G::NL2];
+    auto load_half = [&](long long tl, int h, float2 (&stg)[G::NL2]) {
+        chain_load_half<G>(in, tl, h, n_in_valid, tid, stg);
     };
-    auto write_half = [&](const float2 (&stg)[NL2]) {
-#pragma unroll
-        for (int j = 0; j < NL2; j++) {
-            unsigned idx = (unsigned)(tid + j * MDFIR_BLOCK);
-            unsigned i = idx >> 1, vloc = idx & 1u;
-            if (i < elemsP) {
-                unsigned d = (i & 3u) * SUB + (i >> 2);
-                planes[vloc * SPm + d] = stg[j].x;
-                planes[(2 + vloc) * SPm + d] = stg[j].y;
-            }
-        }
+    auto write_half = [&](const float2 (&stg)[G::NL2]) {
+        chain_write_half<G>(planes, tid, stg);
     };
-    /* lane (r16,k4)'s K-walk in a sub-plane: sub = k4, dword offset
-     * wave*64 + 4*r16 + s — stride-1 in s, 16 B aligned at s%4==0 */
-    const unsigned abase = (unsigned)wave * 64 + 4u * r16;
-    const unsigned asub = (unsigned)k4 * SUB;
-    /* b128 A-reads: one ds_read_b128 pair feeds 8 MFMAs (4 K-steps x
-     * re/im), cutting the per-MFMA issue overhead (round-1 b32 reads:
-     * SQ_WAIT_INST_ANY-heavy, profiles/pmc_sq_r02.txt). One accumulator
-     * pair, re/im alternating: same-C spacing = 2 MFMA issues = 64
-     * cyc/SIMD >= the 40-cyc dependent latency, so extra accumulator
-     * pairs only cost registers (measured: dual pairs were ~3% slower,
-     * forcing 8 waves/SIMD via VGPR caps 2x slower from spills). */
     auto mfma_half = [&](int h, v4f& cre, v4f& cim) {
-#pragma unroll
-        for (int vloc = 0; vloc < 2; vloc++) {
-            const float* pre = planes + (unsigned)vloc * SPm + asub;
-            const float* pim = planes + (unsigned)(2 + vloc) * SPm + asub;
-            const int v = 2 * h + vloc;
-            float bfrag[KKD / 4];
-#pragma unroll
-            for (int s = 0; s < KKD / 4; s++)
-                bfrag[s] = s_rtx[v * (KKD + 16) + 15 + 4 * s + k4 - r16];
-            __builtin_amdgcn_s_setprio(1); /* boost MFMA waves over the
-                                              FFT/staging phases of
-                                              co-resident blocks (T5) */
-#pragma unroll
-            for (int t = 0; t < (KKD / 4) / 4; t++) {
-                float4 ar = *(const float4*)&pre[abase + 4 * t];
-                float4 ai = *(const float4*)&pim[abase + 4 * t];
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.x, bfrag[4 * t], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.x, bfrag[4 * t], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.y, bfrag[4 * t + 1], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.y, bfrag[4 * t + 1], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.z, bfrag[4 * t + 2], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.z, bfrag[4 * t + 2], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.w, bfrag[4 * t + 3], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.w, bfrag[4 * t + 3], cim, 0, 0, 0);
-            }
-#pragma unroll
-            for (int s = (KKD / 4) & ~3; s < KKD / 4; s++) {
-                float a_re = pre[abase + s];
-                float a_im = pim[abase + s];
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    a_re, bfrag[s], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    a_im, bfrag[s], cim, 0, 0, 0);
-            }
-            __builtin_amdgcn_s_setprio(0);
-        }
+        chain_mfma_half<G>(planes, s_rtx, h, ln, cre, cim);
     };
 
     load_half(blockIdx.x, 0, stgA);
     for (long long tile = blockIdx.x;
-         tile * (long long)MDFIR_TILE < n_out; tile += gridDim.x) {
-        const long long out_base = tile * MDFIR_TILE;
+         tile * (long long)G::TILE < n_out; tile += gridDim.x) {
         v4f cre = {0.f, 0.f, 0.f, 0.f};
         v4f cim = {0.f, 0.f, 0.f, 0.f};
         write_half(stgA);
@@ -961,17 +1100,21 @@ __global__ __launch_bounds__(MDFIR_BLOCK, MINWG) void k_decim4_fft_mfma_tpl(
         __syncthreads();
         write_half(stgB);
         __syncthreads();
-        if ((tile + gridDim.x) * (long long)MDFIR_TILE < n_out)
+        if ((tile + gridDim.x) * (long long)G::TILE < n_out)
             load_half(tile + gridDim.x, 0, stgA); /* under half-1 MFMAs */
         mfma_half(1, cre, cim);
         __syncthreads(); /* phase planes are dead; reuse them as FFT LDS */
+        static_assert(G::TILE == 1024, "tile == 1024 decimated outputs");
+        static_assert(2 * 1024 * 2 <= 4 * G::SPm,
+                      "ping + pong (2 x 1024 float2) fit in 4 phase planes");
+        const long long out_base = tile * G::TILE;
         float2* ping = (float2*)planes;       /* 1024 float2 = 8 KB */
-        float2* pong = ping + 1024;           /* fits in 4*SPm floats */
+        float2* pong = ping + 1024;
         const unsigned Lm = (unsigned)fft_len - 1u;
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            int row = k4 * 4 + q;
-            unsigned pos = wave * 256 + 16 * row + r16; /* y2 idx in tile */
+            int row = ln.k4 * 4 + q;
+            unsigned pos = ln.wave * 256 + 16 * row + ln.r16; /* y2 idx */
             ping[(pos & ~Lm) | fft_swz(pos & Lm)] =
                 make_float2(cre[q], cim[q]);
         }
@@ -998,71 +1141,6 @@ __global__ __launch_bounds__(MDFIR_BLOCK, MINWG) void k_decim4_fft_mfma_tpl(
     }
 }
 
-/* Staging loader of the ap and ws chain kernels: tile tl's aligned
- * 4-sample groups q = tid + j*MDFIR_BLOCK (group q = x[4q..4q+3] past the
- * tile base = two 16B loads) into stqa[j]/stqb[j]; samples at or past
- * n_in_valid read as zero.
- *
- * Interior tiles — every sample the tile stages lies below n_in_valid, a
- * block-uniform test — take a straight-line path: all 2*NG loads issue
- * back to back and the consumer waits with counted vmcnt as it uses each
- * group. The last j keeps its q < GROUPS lane predicate (exec mask only,
- * no else-arm), so nothing past the staged range is fetched. With the
- * per-lane guard on every group instead, its else-arm's narrow loads share
- * destination registers with the wide ones and the compiler drains
- * vmcnt(0) before each group: NG dependent HBM round trips per tile
- * (profiles/chain_staging_loads.txt). Only boundary tiles pay that now. */
-template <int KKD, int NG>
-__device__ __forceinline__ void chain_stage_load(
-    const float2* __restrict__ in, long long tl, long long n_in_valid,
-    int tid, float4 (&stqa)[NG], float4 (&stqb)[NG]) {
-    constexpr unsigned GROUPS = (MDFIR_TILE + KKD + 8) + 1;
-    static_assert(NG == (GROUPS + MDFIR_BLOCK - 1) / MDFIR_BLOCK, "NG");
-    const long long qb = tl * MDFIR_TILE;
-    if ((qb + GROUPS) * 4 <= n_in_valid) {
-        const float4* p = (const float4*)(in + (qb + tid) * 4);
-#pragma unroll
-        for (int j = 0; j < NG; j++) {
-            float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-            float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-            if ((unsigned)(j + 1) * MDFIR_BLOCK <= GROUPS ||
-                (unsigned)(tid + j * MDFIR_BLOCK) < GROUPS) {
-                a = p[2 * j * MDFIR_BLOCK];
-                b = p[2 * j * MDFIR_BLOCK + 1];
-            }
-            stqa[j] = a;
-            stqb[j] = b;
-        }
-        return;
-    }
-#pragma unroll
-    for (int j = 0; j < NG; j++) {
-        unsigned q = (unsigned)(tid + j * MDFIR_BLOCK);
-        float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 b = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (q < GROUPS) {
-            long long xq = (qb + q) * 4;
-            if (xq + 3 < n_in_valid) {
-                a = *(const float4*)&in[xq];
-                b = *(const float4*)&in[xq + 2];
-            } else {
-                float2 e0 = (xq < n_in_valid) ? in[xq]
-                                              : make_float2(0.f, 0.f);
-                float2 e1 = (xq + 1 < n_in_valid)
-                                ? in[xq + 1] : make_float2(0.f, 0.f);
-                float2 e2 = (xq + 2 < n_in_valid)
-                                ? in[xq + 2] : make_float2(0.f, 0.f);
-                float2 e3 = (xq + 3 < n_in_valid)
-                                ? in[xq + 3] : make_float2(0.f, 0.f);
-                a = make_float4(e0.x, e0.y, e1.x, e1.y);
-                b = make_float4(e2.x, e2.y, e3.x, e3.y);
-            }
-        }
-        stqa[j] = a;
-        stqb[j] = b;
-    }
-}
-
 /* All-phase staging variant (FSDR_CHAIN_ALLPHASE=1): all 4 phase planes
  * resident at once (8 planes, ~36 KB LDS -> 4 blocks/CU instead of 6),
  * ONE staging write + barrier per tile and a contiguous 160-MFMA run —
@@ -1076,123 +1154,49 @@ __global__ __launch_bounds__(MDFIR_BLOCK) void k_decim4_fft_mfma_ap_tpl(
     const float2* __restrict__ twid /* fft_len-entry forward table */,
     float* __restrict__ mag_out /* nullable |X|^2 */,
     int fft_len) {
-    static_assert(KKD % 4 == 0, "KKD must be a multiple of 4");
-    const unsigned elemsP = MDFIR_TILE + KKD + 8;
-    const unsigned SPm = (elemsP + 31u) & ~31u;
-    const unsigned SUB = SPm / 4;
+    using G = ChainGeom<KKD>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* planes = (float*)smem;        /* [8][SPm]: re v0..3, im v0..3 */
-    float* s_rtx = planes + 8u * SPm;    /* [4][KKD+16] */
+    float* s_rtx = planes + G::ap_rtx;   /* [4][KKD+16] */
+    const chain_lane ln = chain_lane_of<G>(threadIdx.x);
+    const int tid = ln.tid;
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int r16 = lane & 15;
-    const int k4 = lane >> 4;
-
-    for (int i = tid; i < 4 * (KKD + 16); i += MDFIR_BLOCK) {
-        int v = i / (KKD + 16), t = i % (KKD + 16);
-        s_rtx[i] = (t >= 15 && t < 15 + KKD) ? rtv[v * KKD + (t - 15)] : 0.f;
-    }
+    chain_load_taps<G>(s_rtx, rtv, tid);
     __syncthreads();
 
-    /* Staging by ALIGNED 4-sample groups: group q = x[4q..4q+3] = two
-     * 16B float4 loads (x is 32B-aligned at 4q when the base pointer is
-     * 16B-aligned — host guards). Sample x[4q+w] belongs to phase
-     * v=(w+1)&3 at position q (w==3) or q-1 (w<3), since
-     * P_v[i] = x[3+v+4i]. Halves the VMEM instruction count vs float2
-     * loads — the incremental ubench showed the staging loads cost ~25
-     * points of MFMA-pipe utilization (issue/latency interference). */
-    constexpr unsigned GROUPS = (MDFIR_TILE + KKD + 8) + 1;
-    constexpr int NG = (GROUPS + MDFIR_BLOCK - 1) / MDFIR_BLOCK;
-    float4 stqa[NG], stqb[NG];
+    float4 stqa[G::NG], stqb[G::NG];
     auto load_all = [&](long long tl) {
-        chain_stage_load<KKD, NG>(in, tl, n_in_valid, tid, stqa, stqb);
+        chain_stage_load<G>(in, tl, n_in_valid, tid, stqa, stqb);
     };
     auto write_all = [&]() {
-#pragma unroll
-        for (int j = 0; j < NG; j++) {
-            unsigned q = (unsigned)(tid + j * MDFIR_BLOCK);
-            if (q >= GROUPS) continue;
-            float4 a = stqa[j], b = stqb[j];
-            if (q >= 1) { /* w=0,1,2 -> phases 1,2,3 at position q-1 */
-                unsigned d1 = ((q - 1) & 3u) * SUB + ((q - 1) >> 2);
-                planes[1u * SPm + d1] = a.x;
-                planes[5u * SPm + d1] = a.y;
-                planes[2u * SPm + d1] = a.z;
-                planes[6u * SPm + d1] = a.w;
-                planes[3u * SPm + d1] = b.x;
-                planes[7u * SPm + d1] = b.y;
-            }
-            if (q < elemsP) { /* w=3 -> phase 0 at position q */
-                unsigned d0 = (q & 3u) * SUB + (q >> 2);
-                planes[0u * SPm + d0] = b.z;
-                planes[4u * SPm + d0] = b.w;
-            }
-        }
+        chain_write_all<G, false>(planes, tid, stqa, stqb);
     };
-    const unsigned abase = (unsigned)wave * 64 + 4u * r16;
-    const unsigned asub = (unsigned)k4 * SUB;
 
     load_all(blockIdx.x);
     for (long long tile = blockIdx.x;
-         tile * (long long)MDFIR_TILE < n_out; tile += gridDim.x) {
-        const long long out_base = tile * MDFIR_TILE;
+         tile * (long long)G::TILE < n_out; tile += gridDim.x) {
         v4f cre = {0.f, 0.f, 0.f, 0.f};
         v4f cim = {0.f, 0.f, 0.f, 0.f};
         write_all();
         __syncthreads();
-        if ((tile + gridDim.x) * (long long)MDFIR_TILE < n_out)
+        if ((tile + gridDim.x) * (long long)G::TILE < n_out)
             load_all(tile + gridDim.x); /* under this tile's MFMAs */
 #pragma unroll
-        for (int v = 0; v < 4; v++) {
-            const float* pre = planes + (unsigned)v * SPm + asub;
-            const float* pim = planes + (4u + v) * SPm + asub;
-            float bfrag[KKD / 4];
-#pragma unroll
-            for (int s = 0; s < KKD / 4; s++)
-                bfrag[s] = s_rtx[v * (KKD + 16) + 15 + 4 * s + k4 - r16];
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int t = 0; t < (KKD / 4) / 4; t++) {
-                float4 ar = *(const float4*)&pre[abase + 4 * t];
-                float4 ai = *(const float4*)&pim[abase + 4 * t];
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.x, bfrag[4 * t], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.x, bfrag[4 * t], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.y, bfrag[4 * t + 1], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.y, bfrag[4 * t + 1], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.z, bfrag[4 * t + 2], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.z, bfrag[4 * t + 2], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.w, bfrag[4 * t + 3], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.w, bfrag[4 * t + 3], cim, 0, 0, 0);
-            }
-#pragma unroll
-            for (int s = (KKD / 4) & ~3; s < KKD / 4; s++) {
-                float a_re = pre[abase + s];
-                float a_im = pim[abase + s];
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    a_re, bfrag[s], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    a_im, bfrag[s], cim, 0, 0, 0);
-            }
-            __builtin_amdgcn_s_setprio(0);
-        }
+        for (int v = 0; v < 4; v++)
+            chain_mfma_phase<G>(planes + (unsigned)v * G::SPm,
+                                planes + (4u + v) * G::SPm, s_rtx, v, ln,
+                                cre, cim);
         __syncthreads(); /* planes dead; reuse as FFT LDS */
+        static_assert(2 * 1024 * 2 <= 8 * G::SPm,
+                      "ping + pong (2 x 1024 float2) fit in the planes");
+        const long long out_base = tile * G::TILE;
         float2* ping = (float2*)planes;
         float2* pong = ping + 1024;
         const unsigned Lm = (unsigned)fft_len - 1u;
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            int row = k4 * 4 + q;
-            unsigned pos = wave * 256 + 16 * row + r16;
+            int row = ln.k4 * 4 + q;
+            unsigned pos = ln.wave * 256 + 16 * row + ln.r16;
             ping[(pos & ~Lm) | fft_swz(pos & Lm)] =
                 make_float2(cre[q], cim[q]);
         }
@@ -1241,39 +1245,22 @@ __device__ __forceinline__ unsigned rev4_10(unsigned i) {
     return r;
 }
 
-/* LDS twiddle table of the ws kernel: stage s (0..4) holds 256 >> 2s
- * entries starting at ws_tw_off(s) = 0, 256, 320, 336, 340. */
-#define WS_TW_ENTRIES 341
-__host__ __device__ constexpr unsigned ws_tw_off(int s) {
-    return (1024u - (1024u >> (2 * s))) / 3u;
-}
-
 template <int KKD>
 __global__ __launch_bounds__(MDFIR_BLOCK, 3) void k_decim4_fft_mfma_ws_tpl(
     const float2* __restrict__ in, float2* __restrict__ out,
     const float* __restrict__ rtv, long long n_out, long long n_in_valid,
     const float2* __restrict__ twid /* 1024-entry forward table */,
     float* __restrict__ mag_out) {
-    static_assert(KKD % 4 == 0, "KKD must be a multiple of 4");
-    const unsigned elemsP = MDFIR_TILE + KKD + 8;
-    const unsigned SPm = (elemsP + 31u) & ~31u;
-    const unsigned SUB = SPm / 4;
+    using G = ChainGeom<KKD>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* planes = (float*)smem;            /* [8][SPm] */
-    float* s_rtx = planes + 8u * SPm;        /* [4][KKD+16] */
-    float2* fbuf = (float2*)(s_rtx + 4 * (KKD + 16)); /* 1024 f2, in-place */
-    float2* s_tw = fbuf + 1024;              /* [WS_TW_ENTRIES] */
+    float* planes = (float*)smem;              /* [8][SPm] */
+    float* s_rtx = planes + G::ap_rtx;         /* [4][KKD+16] */
+    float2* fbuf = (float2*)(planes + G::ws_fbuf); /* 1024 f2, in-place */
+    float2* s_tw = fbuf + 1024;                /* [WS_TW_ENTRIES] */
+    const chain_lane ln = chain_lane_of<G>(threadIdx.x);
+    const int tid = ln.tid;
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int r16 = lane & 15;
-    const int k4 = lane >> 4;
-
-    for (int i = tid; i < 4 * (KKD + 16); i += MDFIR_BLOCK) {
-        int v = i / (KKD + 16), t = i % (KKD + 16);
-        s_rtx[i] = (t >= 15 && t < 15 + KKD) ? rtv[v * KKD + (t - 15)] : 0.f;
-    }
+    chain_load_taps<G>(s_rtx, rtv, tid);
     /* The FFT stages' twiddles, once per block: stage s reads
      * twid[q << 2s], q < 256 >> 2s, kept as one compact run per stage
      * (256+64+16+4+1 entries, stage s at ws_tw_off(s)) so a stage's reads
@@ -1286,91 +1273,19 @@ __global__ __launch_bounds__(MDFIR_BLOCK, 3) void k_decim4_fft_mfma_ws_tpl(
     }
     __syncthreads();
 
-    constexpr unsigned GROUPS = (MDFIR_TILE + KKD + 8) + 1;
-    constexpr int NG = (GROUPS + MDFIR_BLOCK - 1) / MDFIR_BLOCK;
-    float4 stqa[NG], stqb[NG];
+    float4 stqa[G::NG], stqb[G::NG];
     auto load_all = [&](long long tl) {
-        chain_stage_load<KKD, NG>(in, tl, n_in_valid, tid, stqa, stqb);
+        chain_stage_load<G>(in, tl, n_in_valid, tid, stqa, stqb);
     };
     auto write_all = [&]() {
-#pragma unroll
-        for (int j = 0; j < NG; j++) {
-            unsigned q = (unsigned)(tid + j * MDFIR_BLOCK);
-            float4 a = stqa[j], b = stqb[j];
-            /* Use the group on every path, not only under the lane
-             * predicates below: the compiler then waits for it here, with
-             * a counted vmcnt, and knows at load_all that no staging load
-             * is pending. With the waits only inside the predicated blocks
-             * it assumed they might have been skipped and drained
-             * vmcnt(0), the output stores included, before reusing these
-             * registers for the next tile's loads. */
-            asm volatile("" ::"v"(a.x), "v"(a.y), "v"(a.z), "v"(a.w),
-                         "v"(b.x), "v"(b.y), "v"(b.z), "v"(b.w));
-            if (q >= GROUPS) continue;
-            if (q >= 1) {
-                unsigned d1 = ((q - 1) & 3u) * SUB + ((q - 1) >> 2);
-                planes[1u * SPm + d1] = a.x;
-                planes[5u * SPm + d1] = a.y;
-                planes[2u * SPm + d1] = a.z;
-                planes[6u * SPm + d1] = a.w;
-                planes[3u * SPm + d1] = b.x;
-                planes[7u * SPm + d1] = b.y;
-            }
-            if (q < elemsP) {
-                unsigned d0 = (q & 3u) * SUB + (q >> 2);
-                planes[0u * SPm + d0] = b.z;
-                planes[4u * SPm + d0] = b.w;
-            }
-        }
+        chain_write_all<G, true>(planes, tid, stqa, stqb);
     };
-    const unsigned abase = (unsigned)wave * 64 + 4u * r16;
-    const unsigned asub = (unsigned)k4 * SUB;
-    /* g0/g1 select a sub-range of the vloc's b128 K-groups so the last
-     * vloc can be split across two FFT-stage windows (tail = run the
-     * non-multiple-of-4 K remainder too) */
-    auto mfma_vloc = [&](int v, v4f& cre, v4f& cim, int g0, int g1,
-                         bool tail) {
-        const float* pre = planes + (unsigned)v * SPm + asub;
-        const float* pim = planes + (4u + v) * SPm + asub;
-        float bfrag[KKD / 4];
-#pragma unroll
-        for (int s = 0; s < KKD / 4; s++)
-            bfrag[s] = s_rtx[v * (KKD + 16) + 15 + 4 * s + k4 - r16];
-        __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int t = 0; t < (KKD / 4) / 4; t++) {
-            if (t < g0 || t >= g1) continue;
-            float4 ar = *(const float4*)&pre[abase + 4 * t];
-            float4 ai = *(const float4*)&pim[abase + 4 * t];
-            cre = __builtin_amdgcn_mfma_f32_16x16x4f32(ar.x, bfrag[4 * t],
-                                                       cre, 0, 0, 0);
-            cim = __builtin_amdgcn_mfma_f32_16x16x4f32(ai.x, bfrag[4 * t],
-                                                       cim, 0, 0, 0);
-            cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                ar.y, bfrag[4 * t + 1], cre, 0, 0, 0);
-            cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                ai.y, bfrag[4 * t + 1], cim, 0, 0, 0);
-            cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                ar.z, bfrag[4 * t + 2], cre, 0, 0, 0);
-            cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                ai.z, bfrag[4 * t + 2], cim, 0, 0, 0);
-            cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                ar.w, bfrag[4 * t + 3], cre, 0, 0, 0);
-            cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                ai.w, bfrag[4 * t + 3], cim, 0, 0, 0);
-        }
-        if (tail) {
-#pragma unroll
-            for (int s = (KKD / 4) & ~3; s < KKD / 4; s++) {
-                float a_re = pre[abase + s];
-                float a_im = pim[abase + s];
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    a_re, bfrag[s], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    a_im, bfrag[s], cim, 0, 0, 0);
-            }
-        }
-        __builtin_amdgcn_s_setprio(0);
+    /* one phase's K-walk, or its b128 groups [g0,g1) */
+    auto mfma_phase = [&](int v, v4f& cre, v4f& cim, int g0, int g1,
+                          bool tail) {
+        chain_mfma_phase<G>(planes + (unsigned)v * G::SPm,
+                            planes + (4u + v) * G::SPm, s_rtx, v, ln, cre,
+                            cim, g0, g1, tail);
     };
     /* one in-place DIF radix-4 stage: 256 butterflies, 1 per thread.
      * Stage s: sub-length L = 1024>>(2s), quarter m = L/4; y_r stored
@@ -1403,17 +1318,18 @@ __global__ __launch_bounds__(MDFIR_BLOCK, 3) void k_decim4_fft_mfma_ws_tpl(
     long long prev_base = 0;
     /* A tile's spectrum leaves the FFT strip at the end of the iteration
      * that finishes its FFT, but is stored only in the next iteration,
-     * between write_all and load_all. VMEM retires in order and vmcnt
-     * counts loads and stores alike: stored where they are read, the
-     * stores would be younger than the staging loads in flight, and
-     * write_all's wait for the last group (vmcnt(0), the number of
-     * stores not being static) would drain them at the loop top, a store
-     * round trip per tile. Stored here they are older than those loads;
-     * write_all's unconditional waits let the compiler issue load_all
-     * behind them without a vmcnt wait, so the next wait they meet is
-     * the next loop top's (tests/test_chain_isa_cpu.py holds both).
+     * between the staging write and the staging loads. VMEM retires in
+     * order and vmcnt counts loads and stores alike: stored where they
+     * are read, the stores would be younger than the staging loads in
+     * flight, and chain_write_all's wait for the last group (vmcnt(0),
+     * the number of stores not being static) would drain them at the loop
+     * top, a store round trip per tile. Stored here they are older than
+     * those loads; chain_write_all's unconditional waits (PIN) let the
+     * compiler issue chain_stage_load behind them without a vmcnt wait,
+     * so the next wait they meet is the next loop top's
+     * (tests/test_chain_isa_cpu.py holds both).
      * Measured: -92 us of ~3640 on the bench's chain kernel; the wait
-     * ahead of load_all alone, while it was there, cost nothing
+     * ahead of the staging loads alone, while it was there, cost nothing
      * measurable (profiles/chain_staging_loads.txt). */
     float2 held[4] = {};
     bool have_held = false;
@@ -1436,8 +1352,8 @@ __global__ __launch_bounds__(MDFIR_BLOCK, 3) void k_decim4_fft_mfma_ws_tpl(
         if (have_prev) { /* deposit C(prev) into the FFT strip */
 #pragma unroll
             for (int q = 0; q < 4; q++) {
-                int row = k4 * 4 + q;
-                unsigned pos = wave * 256 + 16 * row + r16;
+                int row = ln.k4 * 4 + q;
+                unsigned pos = ln.wave * 256 + 16 * row + ln.r16;
                 fbuf[fft_swz(pos)] = make_float2(cre[q], cim[q]);
             }
         }
@@ -1447,21 +1363,21 @@ __global__ __launch_bounds__(MDFIR_BLOCK, 3) void k_decim4_fft_mfma_ws_tpl(
             load_all(tile + gridDim.x);
         cre = (v4f){0.f, 0.f, 0.f, 0.f};
         cim = (v4f){0.f, 0.f, 0.f, 0.f};
-        constexpr int G = (KKD / 4) / 4;
-        constexpr int GH = G / 2;
-        mfma_vloc(0, cre, cim, 0, G, true);
+        constexpr int NB = (KKD / 4) / 4; /* b128 groups per phase */
+        constexpr int GH = NB / 2;
+        mfma_phase(0, cre, cim, 0, NB, true);
         if (have_prev) fft_stage(0);
         __syncthreads();
-        mfma_vloc(1, cre, cim, 0, G, true);
+        mfma_phase(1, cre, cim, 0, NB, true);
         if (have_prev) fft_stage(1);
         __syncthreads();
-        mfma_vloc(2, cre, cim, 0, G, true);
+        mfma_phase(2, cre, cim, 0, NB, true);
         if (have_prev) fft_stage(2);
         __syncthreads();
-        mfma_vloc(3, cre, cim, 0, GH, false);
+        mfma_phase(3, cre, cim, 0, GH, false);
         if (have_prev) fft_stage(3);
         __syncthreads();
-        mfma_vloc(3, cre, cim, GH, G, true);
+        mfma_phase(3, cre, cim, GH, NB, true);
         if (have_prev) fft_stage(4);
         __syncthreads();
         if (have_prev) { /* spectrum of prev: out of the strip, held */
@@ -1481,8 +1397,8 @@ __global__ __launch_bounds__(MDFIR_BLOCK, 3) void k_decim4_fft_mfma_ws_tpl(
     if (have_prev) {
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            int row = k4 * 4 + q;
-            unsigned pos = wave * 256 + 16 * row + r16;
+            int row = ln.k4 * 4 + q;
+            unsigned pos = ln.wave * 256 + 16 * row + ln.r16;
             fbuf[fft_swz(pos)] = make_float2(cre[q], cim[q]);
         }
         __syncthreads();
@@ -1501,6 +1417,8 @@ __global__ __launch_bounds__(MDFIR_BLOCK, 3) void k_decim4_fft_mfma_ws_tpl(
     }
 }
 
+/* 512-thread experiment (FSDR_CHAIN_BLOCK512): the halves tile loop at
+ * twice the block and tile, two 1024-pt FFT frames per tile. */
 template <int KKD>
 __global__ __launch_bounds__(512) void k_decim4_fft_mfma2_tpl(
     const float2* __restrict__ in, float2* __restrict__ out,
@@ -1508,125 +1426,33 @@ __global__ __launch_bounds__(512) void k_decim4_fft_mfma2_tpl(
     long long n_out, long long n_in_valid,
     const float2* __restrict__ twid /* 1024-entry forward table */,
     float* __restrict__ mag_out /* nullable |X|^2 */) {
-    static_assert(true, "two 1024-pt FFT frames per tile");
-    static_assert(KKD % 4 == 0, "KKD must be a multiple of 4");
-    const unsigned elemsP = 2048 + KKD + 8;     /* per phase plane */
-    const unsigned SPm = (elemsP + 31u) & ~31u;
-    /* each phase plane is split into 4 sub-planes by element%4 so a
-     * lane's MFMA K-walk (idx = ab+4s) becomes stride-1: one
-     * ds_read_b128 feeds 4 K-steps (the b32-per-MFMA A-reads were the
-     * round-1 issue-stall, SQ_WAIT_INST_ANY 46% — profiles/pmc_r02) */
-    const unsigned SUB = SPm / 4;
+    using G = ChainGeom<KKD, 512, 2048>;
+    static_assert(G::TILE == 2 * 1024 && G::BLOCK == 2 * 256,
+                  "two 1024-pt FFT frames per tile, 256 threads each");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    /* two phases resident at a time ([re_v0, re_v1, im_v0, im_v1]) —
-     * halves LDS vs all-phase planes, doubling resident blocks/CU;
-     * accumulators carry across the two halves, and each half's global
-     * loads are issued under the other half's MFMAs. */
-    float* planes = (float*)smem;        /* [4][SPm] */
-    float* s_rtx = planes + 4u * SPm;    /* [4][KKD+16], 15-zero prologue */
+    float* planes = (float*)smem;           /* [4][SPm] */
+    float* s_rtx = planes + G::halves_rtx;  /* [4][KKD+16] */
+    const chain_lane ln = chain_lane_of<G>(threadIdx.x);
+    const int tid = ln.tid;
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int r16 = lane & 15;
-    const int k4 = lane >> 4;
-
-    for (int i = tid; i < 4 * (KKD + 16); i += 512) {
-        int v = i / (KKD + 16), t = i % (KKD + 16);
-        s_rtx[i] = (t >= 15 && t < 15 + KKD) ? rtv[v * KKD + (t - 15)] : 0.f;
-    }
+    chain_load_taps<G>(s_rtx, rtv, tid);
     __syncthreads();
 
-    const unsigned span = 3 + 4 * elemsP; /* input elements per tile */
-    constexpr int NL2 =
-        (2 * (2048 + KKD + 8) + 3 + 512 - 1) / 512;
-    float2 stgA[NL2], stgB[NL2];
-    /* elements of phases {2h, 2h+1}: rel = 3 + 4i + 2h + vloc */
-    auto load_half = [&](long long tl, int h, float2 (&stg)[NL2]) {
-        const long long ib = tl * 2048 * 4;
-#pragma unroll
-        for (int j = 0; j < NL2; j++) {
-            unsigned idx = (unsigned)(tid + j * 512);
-            unsigned rel = 3 + 4 * (idx >> 1) + 2 * h + (idx & 1u);
-            long long g = ib + rel;
-            stg[j] = (rel < span && g < n_in_valid)
-                         ? in[g] : make_float2(0.f, 0.f);
-        }
+    float2 stgA[G::NL2], stgB[G::NL2];
+    auto load_half = [&](long long tl, int h, float2 (&stg)[G::NL2]) {
+        chain_load_half<G>(in, tl, h, n_in_valid, tid, stg);
     };
-    auto write_half = [&](const float2 (&stg)[NL2]) {
-#pragma unroll
-        for (int j = 0; j < NL2; j++) {
-            unsigned idx = (unsigned)(tid + j * 512);
-            unsigned i = idx >> 1, vloc = idx & 1u;
-            if (i < elemsP) {
-                unsigned d = (i & 3u) * SUB + (i >> 2);
-                planes[vloc * SPm + d] = stg[j].x;
-                planes[(2 + vloc) * SPm + d] = stg[j].y;
-            }
-        }
+    auto write_half = [&](const float2 (&stg)[G::NL2]) {
+        chain_write_half<G>(planes, tid, stg);
     };
-    /* lane (r16,k4)'s K-walk in a sub-plane: sub = k4, dword offset
-     * wave*64 + 4*r16 + s — stride-1 in s, 16 B aligned at s%4==0 */
-    const unsigned abase = (unsigned)wave * 64 + 4u * r16;
-    const unsigned asub = (unsigned)k4 * SUB;
-    /* b128 A-reads: one ds_read_b128 pair feeds 8 MFMAs (4 K-steps x
-     * re/im), cutting the per-MFMA issue overhead (round-1 b32 reads:
-     * SQ_WAIT_INST_ANY-heavy, profiles/pmc_sq_r02.txt). One accumulator
-     * pair, re/im alternating: same-C spacing = 2 MFMA issues = 64
-     * cyc/SIMD >= the 40-cyc dependent latency, so extra accumulator
-     * pairs only cost registers (measured: dual pairs were ~3% slower,
-     * forcing 8 waves/SIMD via VGPR caps 2x slower from spills). */
     auto mfma_half = [&](int h, v4f& cre, v4f& cim) {
-#pragma unroll
-        for (int vloc = 0; vloc < 2; vloc++) {
-            const float* pre = planes + (unsigned)vloc * SPm + asub;
-            const float* pim = planes + (unsigned)(2 + vloc) * SPm + asub;
-            const int v = 2 * h + vloc;
-            float bfrag[KKD / 4];
-#pragma unroll
-            for (int s = 0; s < KKD / 4; s++)
-                bfrag[s] = s_rtx[v * (KKD + 16) + 15 + 4 * s + k4 - r16];
-            __builtin_amdgcn_s_setprio(1); /* boost MFMA waves over the
-                                              FFT/staging phases of
-                                              co-resident blocks (T5) */
-#pragma unroll
-            for (int t = 0; t < (KKD / 4) / 4; t++) {
-                float4 ar = *(const float4*)&pre[abase + 4 * t];
-                float4 ai = *(const float4*)&pim[abase + 4 * t];
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.x, bfrag[4 * t], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.x, bfrag[4 * t], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.y, bfrag[4 * t + 1], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.y, bfrag[4 * t + 1], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.z, bfrag[4 * t + 2], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.z, bfrag[4 * t + 2], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.w, bfrag[4 * t + 3], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.w, bfrag[4 * t + 3], cim, 0, 0, 0);
-            }
-#pragma unroll
-            for (int s = (KKD / 4) & ~3; s < KKD / 4; s++) {
-                float a_re = pre[abase + s];
-                float a_im = pim[abase + s];
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    a_re, bfrag[s], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    a_im, bfrag[s], cim, 0, 0, 0);
-            }
-            __builtin_amdgcn_s_setprio(0);
-        }
+        chain_mfma_half<G>(planes, s_rtx, h, ln, cre, cim);
     };
 
     load_half(blockIdx.x, 0, stgA);
     for (long long tile = blockIdx.x;
-         tile * (long long)2048 < n_out; tile += gridDim.x) {
-        const long long out_base = tile * 2048;
+         tile * (long long)G::TILE < n_out; tile += gridDim.x) {
+        const long long out_base = tile * G::TILE;
         v4f cre = {0.f, 0.f, 0.f, 0.f};
         v4f cim = {0.f, 0.f, 0.f, 0.f};
         write_half(stgA);
@@ -1636,16 +1462,18 @@ __global__ __launch_bounds__(512) void k_decim4_fft_mfma2_tpl(
         __syncthreads();
         write_half(stgB);
         __syncthreads();
-        if ((tile + gridDim.x) * (long long)2048 < n_out)
+        if ((tile + gridDim.x) * (long long)G::TILE < n_out)
             load_half(tile + gridDim.x, 0, stgA); /* under half-1 MFMAs */
         mfma_half(1, cre, cim);
         __syncthreads(); /* phase planes are dead; reuse them as FFT LDS:
                             frame f ping = fbase + f*2048, pong = +1024 */
+        static_assert(2 * 2048 * 2 <= 4 * G::SPm,
+                      "2 frames x (ping + pong) fit in 4 phase planes");
         float2* fbase = (float2*)planes; /* 4096 float2 = 32 KB */
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            int row = k4 * 4 + q;
-            int pos = wave * 256 + 16 * row + r16; /* y2 index in tile */
+            int row = ln.k4 * 4 + q;
+            int pos = ln.wave * 256 + 16 * row + ln.r16; /* y2 index in tile */
             int fr = pos >> 10, idx = pos & 1023;
             fbase[fr * 2048 + fft_swz((unsigned)idx)] =
                 make_float2(cre[q], cim[q]);
@@ -1656,7 +1484,7 @@ __global__ __launch_bounds__(512) void k_decim4_fft_mfma2_tpl(
             fft1024_block(fbase + fl * 2048, fbase + fl * 2048 + 1024,
                           twid, tf);
         }
-        for (int i = tid; i < 2048; i += 512) {
+        for (int i = tid; i < G::TILE; i += G::BLOCK) {
             long long o = out_base + i;
             if (o < n_out) {
                 int fr = i >> 10, idx = i & 1023;
@@ -1671,115 +1499,65 @@ __global__ __launch_bounds__(512) void k_decim4_fft_mfma2_tpl(
 
 /* MFMA-loop microbenchmark (tools/mfma_ubench.py): the decim kernel's
  * inner loop on LDS staged ONCE — no per-tile staging, no FFT, no
- * barriers in the hot loop. Measures the intrinsic ceiling of the
- * b128-fed 16x16x4-f32 loop at this occupancy. */
+ * barriers in the hot loop, no setprio, b128 groups only (no K tail).
+ * Measures the intrinsic ceiling of the b128-fed 16x16x4-f32 loop at
+ * this occupancy. */
 template <int KKD>
 __global__ __launch_bounds__(MDFIR_BLOCK) void k_mfma_ubench_tpl(
     const float* __restrict__ rtv, float2* __restrict__ out, int iters) {
-    const unsigned elemsP = MDFIR_TILE + KKD + 8;
-    const unsigned SPm = (elemsP + 31u) & ~31u;
-    const unsigned SUB = SPm / 4;
+    using G = ChainGeom<KKD>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* planes = (float*)smem;
-    float* s_rtx = planes + 4u * SPm;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int r16 = lane & 15;
-    const int k4 = lane >> 4;
-    for (int i = tid; i < 4 * (KKD + 16); i += MDFIR_BLOCK) {
-        int v = i / (KKD + 16), t = i % (KKD + 16);
-        s_rtx[i] = (t >= 15 && t < 15 + KKD) ? rtv[v * KKD + (t - 15)] : 0.f;
-    }
-    for (int i = tid; i < (int)(4 * SPm); i += MDFIR_BLOCK)
+    float* s_rtx = planes + G::halves_rtx;
+    const chain_lane ln = chain_lane_of<G>(threadIdx.x);
+    const int tid = ln.tid;
+    chain_load_taps<G>(s_rtx, rtv, tid);
+    for (int i = tid; i < (int)(4 * G::SPm); i += MDFIR_BLOCK)
         planes[i] = (float)(i & 255) * 0.001f;
     __syncthreads();
-    const unsigned abase = (unsigned)wave * 64 + 4u * r16;
-    const unsigned asub = (unsigned)k4 * SUB;
     v4f cre = {0.f, 0.f, 0.f, 0.f};
     v4f cim = {0.f, 0.f, 0.f, 0.f};
     for (int it = 0; it < iters; it++) {
 #pragma unroll
-        for (int vloc = 0; vloc < 2; vloc++) {
-            const float* pre = planes + (unsigned)vloc * SPm + asub;
-            const float* pim = planes + (unsigned)(2 + vloc) * SPm + asub;
-            const int v = 2 * ((it ^ vloc) & 1) + vloc;
-            float bfrag[KKD / 4];
-#pragma unroll
-            for (int s = 0; s < KKD / 4; s++)
-                bfrag[s] = s_rtx[v * (KKD + 16) + 15 + 4 * s + k4 - r16];
-#pragma unroll
-            for (int t = 0; t < (KKD / 4) / 4; t++) {
-                float4 ar = *(const float4*)&pre[abase + 4 * t];
-                float4 ai = *(const float4*)&pim[abase + 4 * t];
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.x, bfrag[4 * t], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.x, bfrag[4 * t], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.y, bfrag[4 * t + 1], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.y, bfrag[4 * t + 1], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.z, bfrag[4 * t + 2], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.z, bfrag[4 * t + 2], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.w, bfrag[4 * t + 3], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.w, bfrag[4 * t + 3], cim, 0, 0, 0);
-            }
-        }
+        for (int vloc = 0; vloc < 2; vloc++)
+            chain_mfma_phase<G, false>(
+                planes + (unsigned)vloc * G::SPm,
+                planes + (unsigned)(2 + vloc) * G::SPm, s_rtx,
+                2 * ((it ^ vloc) & 1) + vloc, ln, cre, cim, 0,
+                (KKD / 4) / 4, false);
     }
     long long o = (long long)blockIdx.x * MDFIR_BLOCK + tid;
     out[o] = make_float2(cre[0] + cre[1] + cre[2] + cre[3],
                          cim[0] + cim[1] + cim[2] + cim[3]);
 }
 
-/* Incremental chain ubench: the real tile loop with components gated by
+/* Incremental chain ubench: the halves tile loop with components gated by
  * MODE to isolate the integration cost (tools/mfma_ubench.py):
  *   bit0 (1): global staging loads of the real input
  *   bit1 (2): LDS write_half phases + their barriers
  *   bit2 (4): deposit + in-block FFT + output writes
- * MODE 7 == the production kernel shape; MODE 0 ~= the bare loop. */
+ * MODE 7 == the production kernel shape (the same chain_* calls; the K
+ * tail is left out in every mode); MODE 0 ~= the bare loop. */
 template <int KKD, int MODE>
 __global__ __launch_bounds__(MDFIR_BLOCK) void k_chain_ubench_tpl(
     const float2* __restrict__ in, float2* __restrict__ out,
     const float* __restrict__ rtv, long long n_out, long long n_in_valid,
     const float2* __restrict__ twid) {
-    const unsigned elemsP = MDFIR_TILE + KKD + 8;
-    const unsigned SPm = (elemsP + 31u) & ~31u;
-    const unsigned SUB = SPm / 4;
+    using G = ChainGeom<KKD>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* planes = (float*)smem;
-    float* s_rtx = planes + 4u * SPm;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = tid >> 6;
-    const int r16 = lane & 15;
-    const int k4 = lane >> 4;
-    for (int i = tid; i < 4 * (KKD + 16); i += MDFIR_BLOCK) {
-        int v = i / (KKD + 16), t = i % (KKD + 16);
-        s_rtx[i] = (t >= 15 && t < 15 + KKD) ? rtv[v * KKD + (t - 15)] : 0.f;
-    }
-    for (int i = tid; i < (int)(4 * SPm); i += MDFIR_BLOCK)
+    float* s_rtx = planes + G::halves_rtx;
+    const chain_lane ln = chain_lane_of<G>(threadIdx.x);
+    const int tid = ln.tid;
+    chain_load_taps<G>(s_rtx, rtv, tid);
+    for (int i = tid; i < (int)(4 * G::SPm); i += MDFIR_BLOCK)
         planes[i] = (float)(i & 255) * 0.001f;
     __syncthreads();
-    const unsigned span = 3 + 4 * elemsP;
-    constexpr int NL2 =
-        (2 * (MDFIR_TILE + KKD + 8) + 3 + MDFIR_BLOCK - 1) / MDFIR_BLOCK;
+    constexpr int NL2 = G::NL2;
     float2 stgA[NL2], stgB[NL2];
     auto load_half = [&](long long tl, int h, float2 (&stg)[NL2]) {
         if (MODE & 1) {
-            const long long ib = tl * MDFIR_TILE * 4;
-#pragma unroll
-            for (int j = 0; j < NL2; j++) {
-                unsigned idx = (unsigned)(tid + j * MDFIR_BLOCK);
-                unsigned rel = 3 + 4 * (idx >> 1) + 2 * h + (idx & 1u);
-                long long g = ib + rel;
-                stg[j] = (rel < span && g < n_in_valid)
-                             ? in[g] : make_float2(0.f, 0.f);
-            }
+            chain_load_half<G>(in, tl, h, n_in_valid, tid, stg);
         } else {
 #pragma unroll
             for (int j = 0; j < NL2; j++)
@@ -1789,16 +1567,7 @@ __global__ __launch_bounds__(MDFIR_BLOCK) void k_chain_ubench_tpl(
     };
     auto write_half = [&](const float2 (&stg)[NL2]) {
         if (MODE & 2) {
-#pragma unroll
-            for (int j = 0; j < NL2; j++) {
-                unsigned idx = (unsigned)(tid + j * MDFIR_BLOCK);
-                unsigned i = idx >> 1, vloc = idx & 1u;
-                if (i < elemsP) {
-                    unsigned d = (i & 3u) * SUB + (i >> 2);
-                    planes[vloc * SPm + d] = stg[j].x;
-                    planes[(2 + vloc) * SPm + d] = stg[j].y;
-                }
-            }
+            chain_write_half<G>(planes, tid, stg);
         } else { /* keep stg live without LDS traffic */
             float acc = 0.f;
 #pragma unroll
@@ -1806,42 +1575,8 @@ __global__ __launch_bounds__(MDFIR_BLOCK) void k_chain_ubench_tpl(
             if (acc == 1e30f) planes[tid] = acc; /* never taken */
         }
     };
-    const unsigned abase = (unsigned)wave * 64 + 4u * r16;
-    const unsigned asub = (unsigned)k4 * SUB;
     auto mfma_half = [&](int h, v4f& cre, v4f& cim) {
-#pragma unroll
-        for (int vloc = 0; vloc < 2; vloc++) {
-            const float* pre = planes + (unsigned)vloc * SPm + asub;
-            const float* pim = planes + (unsigned)(2 + vloc) * SPm + asub;
-            const int v = 2 * h + vloc;
-            float bfrag[KKD / 4];
-#pragma unroll
-            for (int s = 0; s < KKD / 4; s++)
-                bfrag[s] = s_rtx[v * (KKD + 16) + 15 + 4 * s + k4 - r16];
-            __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-            for (int t = 0; t < (KKD / 4) / 4; t++) {
-                float4 ar = *(const float4*)&pre[abase + 4 * t];
-                float4 ai = *(const float4*)&pim[abase + 4 * t];
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.x, bfrag[4 * t], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.x, bfrag[4 * t], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.y, bfrag[4 * t + 1], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.y, bfrag[4 * t + 1], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.z, bfrag[4 * t + 2], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.z, bfrag[4 * t + 2], cim, 0, 0, 0);
-                cre = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ar.w, bfrag[4 * t + 3], cre, 0, 0, 0);
-                cim = __builtin_amdgcn_mfma_f32_16x16x4f32(
-                    ai.w, bfrag[4 * t + 3], cim, 0, 0, 0);
-            }
-            __builtin_amdgcn_s_setprio(0);
-        }
+        chain_mfma_half<G>(planes, s_rtx, h, ln, cre, cim, false);
     };
     load_half(blockIdx.x, 0, stgA);
     for (long long tile = blockIdx.x;
@@ -1865,8 +1600,8 @@ __global__ __launch_bounds__(MDFIR_BLOCK) void k_chain_ubench_tpl(
             float2* pong = ping + 1024;
 #pragma unroll
             for (int q = 0; q < 4; q++) {
-                int row = k4 * 4 + q;
-                unsigned pos = wave * 256 + 16 * row + r16;
+                int row = ln.k4 * 4 + q;
+                unsigned pos = ln.wave * 256 + 16 * row + ln.r16;
                 ping[fft_swz(pos)] = make_float2(cre[q], cim[q]);
             }
             __syncthreads();
@@ -1877,26 +1612,44 @@ __global__ __launch_bounds__(MDFIR_BLOCK) void k_chain_ubench_tpl(
             }
             __syncthreads();
         } else {
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                int row = k4 * 4 + q;
-                long long o =
-                    out_base + (long long)wave * 256 + 16 * row + r16;
-                if (o < n_out) out[o] = make_float2(cre[q], cim[q]);
-            }
+            chain_store_rows(out, out_base, n_out, ln, cre, cim);
             if (MODE & 2) __syncthreads();
         }
     }
 }
 
+/* ---- template-size tables and their dispatch -------------------------- *
+ * Each templated kernel family is instantiated for one table of sizes,
+ * stated once here. The create functions pick the smallest entry that
+ * fits (tpl_at_least, 0 if none does); the launchers map the stored
+ * runtime value back onto the compile-time constant: tpl_dispatch calls
+ * f(std::integral_constant<int, K>) for the matching K, or returns false. */
+template <int... Ks>
+struct tpl_table {};
+using fir_tpl_tps = tpl_table<17, 33, 65, 129, 257, 513>;   /* TP >= T */
+using fir_mfma_ks = tpl_table<32, 64, 96, 144, 272, 528>;   /* K >= T+15 */
+using fir_mfma32_ks = tpl_table<48, 96, 160, 288, 544>;     /* K >= T+31 */
+using decim4_tpl_tpds = tpl_table<8, 16, 32, 64, 128>;      /* 4*TPD >= T */
+/* D=4 MFMA family: per-phase K = ceil(T/4)+15 rounded to 4 */
+using decim4_mfma_ks = tpl_table<20, 32, 48, 80, 144>;
+
+template <int... Ks>
+static int tpl_at_least(tpl_table<Ks...>, size_t need) {
+    for (int k : {Ks...})
+        if ((size_t)k >= need) return k;
+    return 0;
+}
+template <int... Ks, class F>
+static bool tpl_dispatch(tpl_table<Ks...>, int k, F&& f) {
+    return ((k == Ks && (f(std::integral_constant<int, Ks>{}), true)) || ...);
+}
+
 extern "C" int fsdr_chain_ubench(int mode, double* tflops, void* stream) {
     REQUIRE_GPU();
-    const int KKD = 80;
+    using G = ChainGeom<80>;
+    const int KKD = G::KKD;
     const long long n_out = 1 << 24; /* decimated outputs (2^26 inputs) */
     const long long n_in = 4 * n_out + 1024;
-    unsigned elemsP = MDFIR_TILE + KKD + 8;
-    unsigned SPm = (elemsP + 31u) & ~31u;
-    size_t lds = (4 * (size_t)SPm + 4 * (KKD + 16)) * sizeof(float);
     float* d_taps = nullptr;
     float2* d_in = nullptr;
     float2* d_out = nullptr;
@@ -1919,25 +1672,17 @@ extern "C" int fsdr_chain_ubench(int mode, double* tflops, void* stream) {
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));
     HIP_TRY(hipEventCreate(&e1));
-#define UB_CASE(MV)                                                       \
-    case MV:                                                              \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME((k_chain_ubench_tpl<80, MV>)), \
-                           dim3(grid), dim3(MDFIR_BLOCK), lds, st, d_in,  \
-                           d_out, d_taps, n_out, n_in, d_tw);             \
-        break;
     for (int rep = 0; rep < 2; rep++) {
         if (rep == 1) HIP_TRY(hipEventRecord(e0, st));
-        switch (mode) {
-            UB_CASE(0)
-            UB_CASE(1)
-            UB_CASE(2)
-            UB_CASE(3)
-            UB_CASE(4)
-            UB_CASE(6)
-            UB_CASE(7)
-            default:
-                set_err("mode must be in {0,1,2,3,4,6,7}");
-                return FSDR_ERR_INVALID;
+        if (!tpl_dispatch(tpl_table<0, 1, 2, 3, 4, 6, 7>{}, mode, [&](auto m) {
+                hipLaunchKernelGGL(
+                    HIP_KERNEL_NAME(
+                        (k_chain_ubench_tpl<G::KKD, decltype(m)::value>)),
+                    dim3(grid), dim3(G::BLOCK), G::halves_bytes, st, d_in,
+                    d_out, d_taps, n_out, n_in, d_tw);
+            })) {
+            set_err("mode must be in {0,1,2,3,4,6,7}");
+            return FSDR_ERR_INVALID;
         }
         HIP_TRY(hipGetLastError());
     }
@@ -1959,10 +1704,9 @@ extern "C" int fsdr_chain_ubench(int mode, double* tflops, void* stream) {
 extern "C" int fsdr_mfma_ubench(int grid, int iters, double* tflops,
                                 void* stream) {
     REQUIRE_GPU();
-    const int KKD = 80;
-    unsigned elemsP = MDFIR_TILE + KKD + 8;
-    unsigned SPm = (elemsP + 31u) & ~31u;
-    size_t lds = (4 * (size_t)SPm + 4 * (KKD + 16)) * sizeof(float);
+    using G = ChainGeom<80>;
+    const int KKD = G::KKD;
+    const size_t lds = G::halves_bytes;
     float* d_taps = nullptr;
     float2* d_out = nullptr;
     HIP_TRY(hipMalloc(&d_taps, 4 * KKD * sizeof(float)));
@@ -3414,10 +3158,7 @@ extern "C" fsdr_filter* fsdr_fir_cf32_create(const float* taps,
     }
     /* template variant: reversed taps zero-filled to the smallest
      * instantiated TP >= n_taps */
-    static const int tps[] = {17, 33, 65, 129, 257, 513};
-    for (int t : tps) {
-        if ((size_t)t >= n_taps) { f->tp_tpl = t; break; }
-    }
+    f->tp_tpl = tpl_at_least(fir_tpl_tps{}, n_taps);
     if (f->tp_tpl) {
         std::vector<float> rt(f->tp_tpl, 0.f);
         for (size_t i = 0; i < n_taps; i++) rt[i] = taps[n_taps - 1 - i];
@@ -3429,9 +3170,7 @@ extern "C" fsdr_filter* fsdr_fir_cf32_create(const float* taps,
             return nullptr;
         }
     }
-    static const int kk32s[] = {48, 96, 160, 288, 544};
-    for (int k : kk32s)
-        if ((size_t)k >= n_taps + 31) { f->kk_mfma32 = k; break; }
+    f->kk_mfma32 = tpl_at_least(fir_mfma32_ks{}, n_taps + 31);
     if (f->kk_mfma32) {
         std::vector<float> rt(f->kk_mfma32, 0.f);
         for (size_t i = 0; i < n_taps; i++) rt[i] = taps[n_taps - 1 - i];
@@ -3444,9 +3183,7 @@ extern "C" fsdr_filter* fsdr_fir_cf32_create(const float* taps,
             return nullptr;
         }
     }
-    static const int kks[] = {32, 64, 96, 144, 272, 528};
-    for (int k : kks)
-        if ((size_t)k >= n_taps + 15) { f->kk_mfma = k; break; }
+    f->kk_mfma = tpl_at_least(fir_mfma_ks{}, n_taps + 15);
     if (f->kk_mfma) {
         std::vector<float> rt(f->kk_mfma, 0.f);
         for (size_t i = 0; i < n_taps; i++) rt[i] = taps[n_taps - 1 - i];
@@ -3515,10 +3252,8 @@ extern "C" fsdr_filter* fsdr_decim_fir_cf32_create(size_t decimation,
     }
     if (decimation == 4 && n_taps <= 512) {
         /* MFMA variant: per-phase K = ceil(T/4)+15 rounded to 4 */
-        static const int kkds[] = {20, 32, 48, 80, 144};
         size_t tpd_true = (n_taps + 3) / 4;
-        for (int k : kkds)
-            if ((size_t)k >= tpd_true + 15) { f->kk_mfma = k; break; }
+        f->kk_mfma = tpl_at_least(decim4_mfma_ks{}, tpd_true + 15);
         if (f->kk_mfma) {
             int kkd = f->kk_mfma;
             std::vector<float> rm(4 * (size_t)kkd, 0.f);
@@ -3539,10 +3274,7 @@ extern "C" fsdr_filter* fsdr_decim_fir_cf32_create(size_t decimation,
             }
         }
         /* phase-split template: rtv[v][u] = h[n_taps-1-(4u+v)] */
-        static const int tpds[] = {8, 16, 32, 64, 128};
-        for (int t : tpds) {
-            if ((size_t)(4 * t) >= n_taps) { f->tp_tpl = t; break; }
-        }
+        f->tp_tpl = tpl_at_least(decim4_tpl_tpds{}, tpd_true);
         int tpd = f->tp_tpl;
         std::vector<float> rtv(4 * (tpd + 4), 0.f);
         for (int v = 0; v < 4; v++)
@@ -4102,18 +3834,16 @@ static int launch_fir_cf32(fsdr_filter* f, const void* d_in, void* d_out,
         unsigned elems32 = MFIR32_TILE + f->kk_mfma32 + 8;
         size_t lds32 = (2 * (size_t)((elems32 + 31u) & ~31u) +
                         f->kk_mfma32 + 36) * sizeof(float);
-#define MFIR32_TPL_CASE(KV)                                                      case KV:                                                                         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fir_mfma32_tpl<KV>),                                       dim3(grid32), dim3(MFIR32_BLOCK), lds32, st,                                 (const float2*)d_in, (float2*)d_out,                                         f->d_mtaps32, (long long)n_out, (long long)n_in);         break;
-        switch (f->kk_mfma32) {
-            MFIR32_TPL_CASE(48)
-            MFIR32_TPL_CASE(96)
-            MFIR32_TPL_CASE(160)
-            MFIR32_TPL_CASE(288)
-            MFIR32_TPL_CASE(544)
-            default:
-                set_err("bad mfma32 K");
-                return FSDR_ERR_INVALID;
+        if (!tpl_dispatch(fir_mfma32_ks{}, f->kk_mfma32, [&](auto K) {
+                hipLaunchKernelGGL(
+                    HIP_KERNEL_NAME(k_fir_mfma32_tpl<decltype(K)::value>),
+                    dim3(grid32), dim3(MFIR32_BLOCK), lds32, st,
+                    (const float2*)d_in, (float2*)d_out, f->d_mtaps32,
+                    (long long)n_out, (long long)n_in);
+            })) {
+            set_err("bad mfma32 K");
+            return FSDR_ERR_INVALID;
         }
-#undef MFIR32_TPL_CASE
         HIP_TRY(hipGetLastError());
         return FSDR_OK;
     }
@@ -4122,19 +3852,16 @@ static int launch_fir_cf32(fsdr_filter* f, const void* d_in, void* d_out,
         unsigned elems = MFIR_TILE + f->kk_mfma + 8;
         size_t lds = (2 * (size_t)((elems + 31u) & ~31u) + f->kk_mfma + 20)
                      * sizeof(float);
-#define MFIR_TPL_CASE(KV)                                                        case KV:                                                                         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fir_mfma_tpl<KV>), dim3(grid),                             dim3(MFIR_BLOCK), lds, st, (const float2*)d_in,                              (float2*)d_out, f->d_mtaps, (long long)n_out,                                (long long)n_in);                                         break;
-        switch (f->kk_mfma) {
-            MFIR_TPL_CASE(32)
-            MFIR_TPL_CASE(64)
-            MFIR_TPL_CASE(96)
-            MFIR_TPL_CASE(144)
-            MFIR_TPL_CASE(272)
-            MFIR_TPL_CASE(528)
-            default:
-                set_err("bad mfma K");
-                return FSDR_ERR_INVALID;
+        if (!tpl_dispatch(fir_mfma_ks{}, f->kk_mfma, [&](auto K) {
+                hipLaunchKernelGGL(
+                    HIP_KERNEL_NAME(k_fir_mfma_tpl<decltype(K)::value>),
+                    dim3(grid), dim3(MFIR_BLOCK), lds, st,
+                    (const float2*)d_in, (float2*)d_out, f->d_mtaps,
+                    (long long)n_out, (long long)n_in);
+            })) {
+            set_err("bad mfma K");
+            return FSDR_ERR_INVALID;
         }
-#undef MFIR_TPL_CASE
         HIP_TRY(hipGetLastError());
         return FSDR_OK;
     }
@@ -4142,19 +3869,16 @@ static int launch_fir_cf32(fsdr_filter* f, const void* d_in, void* d_out,
         unsigned elems = FIR_TILE_OUT + f->tp_tpl + 8;
         size_t lds = (2 * (size_t)((elems + 7u) & ~7u) + f->tp_tpl + 3) *
                      sizeof(float);
-#define FIR_TPL_CASE(TPV)                                                        case TPV:                                                                        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fir_cf32_tpl<TPV>),                                        dim3(grid), dim3(FIR_BLOCK), lds, st,                                        (const float2*)d_in, (float2*)d_out, f->d_rtaps,                             (long long)n_out, (long long)n_in);                       break;
-        switch (f->tp_tpl) {
-            FIR_TPL_CASE(17)
-            FIR_TPL_CASE(33)
-            FIR_TPL_CASE(65)
-            FIR_TPL_CASE(129)
-            FIR_TPL_CASE(257)
-            FIR_TPL_CASE(513)
-            default:
-                set_err("bad template tap count");
-                return FSDR_ERR_INVALID;
+        if (!tpl_dispatch(fir_tpl_tps{}, f->tp_tpl, [&](auto TP) {
+                hipLaunchKernelGGL(
+                    HIP_KERNEL_NAME(k_fir_cf32_tpl<decltype(TP)::value>),
+                    dim3(grid), dim3(FIR_BLOCK), lds, st,
+                    (const float2*)d_in, (float2*)d_out, f->d_rtaps,
+                    (long long)n_out, (long long)n_in);
+            })) {
+            set_err("bad template tap count");
+            return FSDR_ERR_INVALID;
         }
-#undef FIR_TPL_CASE
         HIP_TRY(hipGetLastError());
         return FSDR_OK;
     }
@@ -4176,21 +3900,17 @@ static int launch_decim_cf32(fsdr_filter* f, const void* d_in, void* d_out,
         long long tiles = ((long long)n_out + MDFIR_TILE - 1) / MDFIR_TILE;
         long long cap = grid_cap(256 * 64);
         int grid = (int)std::min<long long>(tiles, cap);
-        unsigned elemsP = MDFIR_TILE + f->kk_mfma + 8;
-        size_t lds = (4 * (size_t)((elemsP + 31u) & ~31u) +
-                      4 * ((size_t)f->kk_mfma + 16)) * sizeof(float);
-#define MDFIR_TPL_CASE(KV)                                                       case KV:                                                                         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_decim4_mfma_tpl<KV>),                                      dim3(grid), dim3(MDFIR_BLOCK), lds, st,                                      (const float2*)d_in, (float2*)d_out, f->d_mtaps,                             (long long)n_out, (long long)n_in);                       break;
-        switch (f->kk_mfma) {
-            MDFIR_TPL_CASE(20)
-            MDFIR_TPL_CASE(32)
-            MDFIR_TPL_CASE(48)
-            MDFIR_TPL_CASE(80)
-            MDFIR_TPL_CASE(144)
-            default:
-                set_err("bad decim mfma K");
-                return FSDR_ERR_INVALID;
+        if (!tpl_dispatch(decim4_mfma_ks{}, f->kk_mfma, [&](auto K) {
+                using G = ChainGeom<decltype(K)::value>;
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_decim4_mfma_tpl<G::KKD>),
+                                   dim3(grid), dim3(G::BLOCK),
+                                   G::halves_bytes, st, (const float2*)d_in,
+                                   (float2*)d_out, f->d_mtaps,
+                                   (long long)n_out, (long long)n_in);
+            })) {
+            set_err("bad decim mfma K");
+            return FSDR_ERR_INVALID;
         }
-#undef MDFIR_TPL_CASE
         HIP_TRY(hipGetLastError());
         return FSDR_OK;
     }
@@ -4200,18 +3920,16 @@ static int launch_decim_cf32(fsdr_filter* f, const void* d_in, void* d_out,
         int grid = (int)std::min<long long>(tiles, cap);
         size_t lds = (4 * (size_t)dfirt_sp(f->tp_tpl) +
                       4 * ((size_t)f->tp_tpl + 4)) * sizeof(float);
-#define DFIR_TPL_CASE(TPV)                                                       case TPV:                                                                        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fir_decim4_tpl<TPV>),                                      dim3(grid), dim3(DFIRT_BLOCK), lds, st,                                      (const float2*)d_in, (float2*)d_out, f->d_rtaps,                             (long long)n_out, (long long)n_in);                       break;
-        switch (f->tp_tpl) {
-            DFIR_TPL_CASE(8)
-            DFIR_TPL_CASE(16)
-            DFIR_TPL_CASE(32)
-            DFIR_TPL_CASE(64)
-            DFIR_TPL_CASE(128)
-            default:
-                set_err("bad decim template tap count");
-                return FSDR_ERR_INVALID;
+        if (!tpl_dispatch(decim4_tpl_tpds{}, f->tp_tpl, [&](auto TPD) {
+                hipLaunchKernelGGL(
+                    HIP_KERNEL_NAME(k_fir_decim4_tpl<decltype(TPD)::value>),
+                    dim3(grid), dim3(DFIRT_BLOCK), lds, st,
+                    (const float2*)d_in, (float2*)d_out, f->d_rtaps,
+                    (long long)n_out, (long long)n_in);
+            })) {
+            set_err("bad decim template tap count");
+            return FSDR_ERR_INVALID;
         }
-#undef DFIR_TPL_CASE
         HIP_TRY(hipGetLastError());
         return FSDR_OK;
     }
@@ -5448,9 +5166,15 @@ extern "C" int fsdr_chain_run_dev(fsdr_chain* c, const void* d_in,
         /* ~2 tiles/block at 2^26: best measured */
         long long cap = grid_cap(8192);
         int grid = (int)std::min<long long>(tiles, cap);
-        unsigned elemsP = MDFIR_TILE + KK + 8;
-        size_t lds = (4 * (size_t)((elemsP + 31u) & ~31u) +
-                      4 * ((size_t)KK + 16)) * sizeof(float);
+        /* a launch of one of the family's kernels at this filter's K */
+        auto chain_launch = [&](auto&& launch) -> int {
+            if (!tpl_dispatch(decim4_mfma_ks{}, KK, launch)) {
+                set_err("bad chain mfma K");
+                return FSDR_ERR_INVALID;
+            }
+            HIP_TRY(hipGetLastError());
+            return FSDR_OK;
+        };
         float2* spec_dst = (float2*)d_out; /* null + mag-only: skip the
                                               discarded spectra write */
         if (!spec_dst && !d_mag) { /* NullSink scratch keeps work observable */
@@ -5464,11 +5188,10 @@ extern "C" int fsdr_chain_run_dev(fsdr_chain* c, const void* d_in,
             prod % 2048 == 0) {
             long long tiles2 = (long long)prod / 2048;
             int grid2 = (int)std::min<long long>(tiles2, cap);
-            unsigned eP2 = 2048 + 80 + 8;
-            size_t lds2 = (4 * (size_t)((eP2 + 31u) & ~31u) + 4 * (80 + 16))
-                          * sizeof(float);
+            using G2 = ChainGeom<80, 512, 2048>;
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_decim4_fft_mfma2_tpl<80>),
-                               dim3(grid2), dim3(512), lds2, st,
+                               dim3(grid2), dim3(G2::BLOCK),
+                               G2::halves_bytes, st,
                                (const float2*)d_in, spec_dst,
                                c->fused->d_mtaps, (long long)prod,
                                (long long)n_in,
@@ -5484,32 +5207,15 @@ extern "C" int fsdr_chain_run_dev(fsdr_chain* c, const void* d_in,
          * aligned 1024 case; FSDR_CHAIN_WS=0 disables. */
         if ((!ws || atoi(ws) != 0) && L == 1024 &&
             ((uintptr_t)d_in & 15u) == 0) {
-            unsigned SPm = (elemsP + 31u) & ~31u;
-            size_t lds_ws = (8 * (size_t)SPm + 4 * ((size_t)KK + 16)) *
-                                sizeof(float) +
-                            (1024 + WS_TW_ENTRIES) * sizeof(float2);
-#define CHAIN_WS_CASE(KV)                                                 \
-    case KV:                                                              \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_decim4_fft_mfma_ws_tpl<KV>), \
-                           dim3(grid), dim3(MDFIR_BLOCK), lds_ws, st,     \
-                           (const float2*)d_in, spec_dst,                 \
-                           c->fused->d_mtaps, (long long)prod,            \
-                           (long long)n_in,                               \
-                           (const float2*)c->fft->d_twid, (float*)d_mag); \
-        break;
-            switch (KK) {
-                CHAIN_WS_CASE(20)
-                CHAIN_WS_CASE(32)
-                CHAIN_WS_CASE(48)
-                CHAIN_WS_CASE(80)
-                CHAIN_WS_CASE(144)
-                default:
-                    set_err("bad chain mfma K");
-                    return FSDR_ERR_INVALID;
-            }
-#undef CHAIN_WS_CASE
-            HIP_TRY(hipGetLastError());
-            return FSDR_OK;
+            return chain_launch([&](auto K) {
+                using G = ChainGeom<decltype(K)::value>;
+                hipLaunchKernelGGL(
+                    HIP_KERNEL_NAME(k_decim4_fft_mfma_ws_tpl<G::KKD>),
+                    dim3(grid), dim3(G::BLOCK), G::ws_bytes, st,
+                    (const float2*)d_in, spec_dst, c->fused->d_mtaps,
+                    (long long)prod, (long long)n_in,
+                    (const float2*)c->fft->d_twid, (float*)d_mag);
+            });
         }
         const char* ap = getenv("FSDR_CHAIN_ALLPHASE");
         /* all-phase + aligned-group staging is the default (measured
@@ -5519,32 +5225,15 @@ extern "C" int fsdr_chain_run_dev(fsdr_chain* c, const void* d_in,
          * offsets can be 8B-odd — so unaligned inputs (and
          * FSDR_CHAIN_ALLPHASE=0) take the 2-phase-halves kernel. */
         if ((!ap || atoi(ap) != 0) && ((uintptr_t)d_in & 15u) == 0) {
-            unsigned SPm = (elemsP + 31u) & ~31u;
-            size_t lds_ap =
-                (8 * (size_t)SPm + 4 * ((size_t)KK + 16)) * sizeof(float);
-#define CHAIN_AP_CASE(KV)                                                 \
-    case KV:                                                              \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_decim4_fft_mfma_ap_tpl<KV>), \
-                           dim3(grid), dim3(MDFIR_BLOCK), lds_ap, st,     \
-                           (const float2*)d_in, spec_dst,                 \
-                           c->fused->d_mtaps, (long long)prod,            \
-                           (long long)n_in,                               \
-                           (const float2*)c->fft->d_twid, (float*)d_mag,  \
-                           (int)L);                                       \
-        break;
-            switch (KK) {
-                CHAIN_AP_CASE(20)
-                CHAIN_AP_CASE(32)
-                CHAIN_AP_CASE(48)
-                CHAIN_AP_CASE(80)
-                CHAIN_AP_CASE(144)
-                default:
-                    set_err("bad chain mfma K");
-                    return FSDR_ERR_INVALID;
-            }
-#undef CHAIN_AP_CASE
-            HIP_TRY(hipGetLastError());
-            return FSDR_OK;
+            return chain_launch([&](auto K) {
+                using G = ChainGeom<decltype(K)::value>;
+                hipLaunchKernelGGL(
+                    HIP_KERNEL_NAME(k_decim4_fft_mfma_ap_tpl<G::KKD>),
+                    dim3(grid), dim3(G::BLOCK), G::ap_bytes, st,
+                    (const float2*)d_in, spec_dst, c->fused->d_mtaps,
+                    (long long)prod, (long long)n_in,
+                    (const float2*)c->fft->d_twid, (float*)d_mag, (int)L);
+            });
         }
         const char* occ8 = getenv("FSDR_CHAIN_OCC8");
         if (occ8 && atoi(occ8) != 0 && KK == 80) {
@@ -5552,7 +5241,8 @@ extern "C" int fsdr_chain_run_dev(fsdr_chain* c, const void* d_in,
              * 64 by the compiler; some spill risk) */
             hipLaunchKernelGGL(
                 HIP_KERNEL_NAME((k_decim4_fft_mfma_tpl<80, 8>)),
-                dim3(grid), dim3(MDFIR_BLOCK), lds, st,
+                dim3(grid), dim3(MDFIR_BLOCK), ChainGeom<80>::halves_bytes,
+                st,
                 (const float2*)d_in, spec_dst, c->fused->d_mtaps,
                 (long long)prod, (long long)n_in,
                 (const float2*)c->fft->d_twid, (float*)d_mag, (int)L, 0);
@@ -5562,29 +5252,15 @@ extern "C" int fsdr_chain_run_dev(fsdr_chain* c, const void* d_in,
         int stagger = 0;
         if (const char* sg = getenv("FSDR_CHAIN_STAGGER"))
             stagger = atoi(sg);
-#define CHAIN_TPL_CASE(KV)                                                \
-    case KV:                                                              \
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_decim4_fft_mfma_tpl<KV>),    \
-                           dim3(grid), dim3(MDFIR_BLOCK), lds, st,        \
-                           (const float2*)d_in, spec_dst,                 \
-                           c->fused->d_mtaps, (long long)prod,            \
-                           (long long)n_in,                               \
-                           (const float2*)c->fft->d_twid, (float*)d_mag,  \
-                           (int)L, stagger);                              \
-        break;
-        switch (KK) {
-            CHAIN_TPL_CASE(20)
-            CHAIN_TPL_CASE(32)
-            CHAIN_TPL_CASE(48)
-            CHAIN_TPL_CASE(80)
-            CHAIN_TPL_CASE(144)
-            default:
-                set_err("bad chain mfma K");
-                return FSDR_ERR_INVALID;
-        }
-#undef CHAIN_TPL_CASE
-        HIP_TRY(hipGetLastError());
-        return FSDR_OK;
+        return chain_launch([&](auto K) {
+            using G = ChainGeom<decltype(K)::value>;
+            hipLaunchKernelGGL(
+                HIP_KERNEL_NAME(k_decim4_fft_mfma_tpl<G::KKD>), dim3(grid),
+                dim3(G::BLOCK), G::halves_bytes, st, (const float2*)d_in,
+                spec_dst, c->fused->d_mtaps, (long long)prod,
+                (long long)n_in, (const float2*)c->fft->d_twid,
+                (float*)d_mag, (int)L, stagger);
+        });
     }
     rc = ensure_dev((void**)&c->d_y2, &c->y2_cap,
                     (prod + 8) * sizeof(float2));
