@@ -108,6 +108,38 @@ def _load():
         fn.restype = ctypes.c_int
         fn.argtypes = [vp, vp, sz, sz, vp, sz, vp, ctypes.POINTER(sz),
                        ctypes.POINTER(sz)]
+    u64 = ctypes.c_uint64
+    u64p = ctypes.POINTER(u64)
+    lib.fsdr_pfb_arb_schedule_create.restype = ctypes.c_int
+    lib.fsdr_pfb_arb_schedule_create.argtypes = [ctypes.c_float, sz,
+                                                 ctypes.POINTER(vp)]
+    lib.fsdr_pfb_arb_schedule_destroy.restype = None
+    lib.fsdr_pfb_arb_schedule_destroy.argtypes = [vp]
+    lib.fsdr_pfb_arb_schedule_info.restype = ctypes.c_int
+    lib.fsdr_pfb_arb_schedule_info.argtypes = [vp, u64p, u64p, u64p,
+                                               ctypes.POINTER(sz),
+                                               ctypes.POINTER(sz)]
+    lib.fsdr_pfb_arb_schedule_count.restype = u64
+    lib.fsdr_pfb_arb_schedule_count.argtypes = [vp, u64, u64]
+    lib.fsdr_pfb_arb_schedule_records.restype = sz
+    lib.fsdr_pfb_arb_schedule_records.argtypes = [vp, u64, sz, vp, vp, vp,
+                                                  vp, sz]
+    lib.fsdr_pfb_arb_schedule_work.restype = None
+    lib.fsdr_pfb_arb_schedule_work.argtypes = [vp, sz, u64, sz, sz,
+                                               ctypes.POINTER(sz),
+                                               ctypes.POINTER(sz)]
+    lib.fsdr_pfb_arb_startup_map.restype = None
+    lib.fsdr_pfb_arb_startup_map.argtypes = [sz, vp]
+    lib.fsdr_pfb_arb_resampler_create.restype = vp
+    lib.fsdr_pfb_arb_resampler_create.argtypes = [ctypes.c_float, f32p, sz,
+                                                  sz, sz]
+    lib.fsdr_pfb_arb_resampler_schedule.restype = vp
+    lib.fsdr_pfb_arb_resampler_schedule.argtypes = [vp]
+    for fn in (lib.fsdr_pfb_arb_resampler_run_dev,
+               lib.fsdr_pfb_arb_resampler_stream_dev):
+        fn.restype = ctypes.c_int
+        fn.argtypes = [vp, vp, sz, sz, vp, sz, sz, vp, ctypes.POINTER(sz),
+                       ctypes.POINTER(sz)]
     lib.fsdr_xlating_fir_cf32_create.restype = vp
     lib.fsdr_xlating_fir_cf32_create.argtypes = [f32p, sz, sz,
                                                  ctypes.c_float,
@@ -578,6 +610,146 @@ class PfbSynthesizer(Filter):
         """One stateful call; returns (out, consumed_per_chan). Steps not
         consumed must be re-presented by the caller."""
         return self._call(_load().fsdr_pfb_synthesizer_stream_dev, chans,
+                          out_cap)
+
+
+def pfb_arb_startup_map(taps_per_filter):
+    """src[s]: the fill push that slot s of the just-filled window holds,
+    -1 for a hole (WindowBuffer::new(len, false)). Needs no GPU."""
+    src = np.zeros(taps_per_filter, np.int64)
+    _load().fsdr_pfb_arb_startup_map(taps_per_filter, _c(src))
+    return src
+
+
+class PfbArbSchedule:
+    """The PfbArbResampler timing schedule for (rate, num_filters): which
+    input yields which outputs, with which filter index and mu. Host-only,
+    needs no GPU. Positions count the pushes after the window fill."""
+
+    def __init__(self, rate, num_filters, _borrowed=None):
+        lib = _load()
+        self._own = _borrowed is None
+        self._destroy = lib.fsdr_pfb_arb_schedule_destroy
+        if self._own:
+            h = ctypes.c_void_p()
+            rc = lib.fsdr_pfb_arb_schedule_create(rate, num_filters,
+                                                  ctypes.byref(h))
+            if rc != OK:
+                err = FsdrError(f"fsdr error {rc}: "
+                                f"{lib.fsdr_last_error().decode()}")
+                err.code = rc
+                raise err
+            self._h = h
+        else:
+            self._h = ctypes.c_void_p(_borrowed)
+        rho, lam, opc = (ctypes.c_uint64() for _ in range(3))
+        q, seg = ctypes.c_size_t(), ctypes.c_size_t()
+        _check(lib.fsdr_pfb_arb_schedule_info(
+            self._h, ctypes.byref(rho), ctypes.byref(lam), ctypes.byref(opc),
+            ctypes.byref(q), ctypes.byref(seg)))
+        self.preperiod, self.period = rho.value, lam.value
+        self.outputs_per_period = opc.value
+        self.checkpoint_spacing = q.value
+        self.segment_inputs = seg.value
+
+    def __del__(self):
+        # may run at interpreter exit, after the module globals are gone
+        if getattr(self, "_own", False) and getattr(self, "_h", None):
+            self._destroy(self._h)
+            self._h = None
+
+    def count(self, pushes_after_fill, n_inputs):
+        return _load().fsdr_pfb_arb_schedule_count(
+            self._h, pushes_after_fill, n_inputs)
+
+    def records(self, first_input, n_inputs):
+        """(in_index u64, base_index u32, boundary u8, mu f32), one entry
+        per output of inputs [first_input, first_input + n_inputs)."""
+        lib = _load()
+        n = lib.fsdr_pfb_arb_schedule_records(
+            self._h, first_input, n_inputs, None, None, None, None, 0)
+        idx = np.zeros(n, np.uint64)
+        base = np.zeros(n, np.uint32)
+        bnd = np.zeros(n, np.uint8)
+        mu = np.zeros(n, np.float32)
+        lib.fsdr_pfb_arb_schedule_records(
+            self._h, first_input, n_inputs, _c(idx), _c(base), _c(bnd),
+            _c(mu), n)
+        return idx, base, bnd, mu
+
+    def work(self, taps_per_filter, pushes, n_in, out_cap):
+        """(consumed, produced) of one resampler call by a stream that has
+        consumed `pushes` inputs in all."""
+        cons, prod = ctypes.c_size_t(), ctypes.c_size_t()
+        _load().fsdr_pfb_arb_schedule_work(
+            self._h, taps_per_filter, pushes, n_in, out_cap,
+            ctypes.byref(cons), ctypes.byref(prod))
+        return cons.value, prod.value
+
+
+class PfbArbResampler(Filter):
+    """PFB arbitrary-rate resampler — pfb/arb_resampler.rs, for
+    num_channels channels in lockstep. chans is [num_channels, T] (or 1-D
+    for one channel); run() is one-shot from zero state, stream() carries
+    the window and the position across calls. Both return
+    ([num_channels, produced] array, consumed_per_chan)."""
+
+    def __init__(self, rate, taps, num_filters, num_channels=1):
+        self._taps_keep, p = _f32(taps)
+        self.rate = float(np.float32(rate))
+        self.n = num_channels
+        super().__init__(_load().fsdr_pfb_arb_resampler_create(
+            rate, p, self._taps_keep.size, num_filters, num_channels))
+
+    @property
+    def schedule(self):
+        """The handle's own schedule (borrowed; keeps the handle alive)."""
+        s = PfbArbSchedule(
+            None, None,
+            _borrowed=_load().fsdr_pfb_arb_resampler_schedule(self._h))
+        s._keep = self
+        return s
+
+    def out_cap_for(self, n_in):
+        """An out_cap_per_chan with which a call takes all n_in inputs."""
+        return int(np.ceil(n_in * self.rate * (1 + 1e-6))) + \
+            int(np.ceil(self.rate)) + 2
+
+    def _call(self, fn, chans, out_cap):
+        lib = _load()
+        chans = np.ascontiguousarray(chans, CF32).reshape(self.n, -1)
+        t = chans.shape[1]
+        if out_cap is None:
+            out_cap = self.out_cap_for(t)
+        d_in = ctypes.c_void_p()
+        d_out = ctypes.c_void_p()
+        _check(lib.fsdr_dev_alloc(ctypes.byref(d_in), chans.size * 8 + 8))
+        _check(lib.fsdr_dev_alloc(ctypes.byref(d_out),
+                                  self.n * out_cap * 8 + 8))
+        try:
+            if chans.size:
+                _check(lib.fsdr_memcpy_h2d(d_in, _c(chans), chans.size * 8))
+            cons = ctypes.c_size_t()
+            prod = ctypes.c_size_t()
+            _check(fn(self._h, d_in, t, t, d_out, out_cap, out_cap, None,
+                      ctypes.byref(cons), ctypes.byref(prod)))
+            _check(lib.fsdr_synchronize())
+            out = np.zeros((self.n, out_cap), CF32)
+            if prod.value:
+                _check(lib.fsdr_memcpy_d2h(_c(out), d_out, out.size * 8))
+            return out[:, :prod.value].copy(), cons.value
+        finally:
+            lib.fsdr_dev_free(d_in)
+            lib.fsdr_dev_free(d_out)
+
+    def run(self, chans, out_cap=None):
+        return self._call(_load().fsdr_pfb_arb_resampler_run_dev, chans,
+                          out_cap)
+
+    def stream(self, chans, out_cap=None):
+        """One stateful call. Inputs not consumed must be re-presented by
+        the caller."""
+        return self._call(_load().fsdr_pfb_arb_resampler_stream_dev, chans,
                           out_cap)
 
 

@@ -5,9 +5,10 @@
  * Written for CDNA4 from scratch: 64-wide wavefronts, LDS-staged FIR tiles
  * with register sliding windows, SoA re/im LDS planes with a 2-dwords-per-16
  * pad (breaks the stride-16B bank pattern of the pair reads), radix-4
- * Stockham FFT in LDS, the PFB channelizer and the PFB synthesizer (one
- * fused gather + in-LDS IFFT + commutator kernel). No CUDA shims, no
- * hipify output.
+ * Stockham FFT in LDS, the PFB channelizer, the PFB synthesizer (one
+ * fused gather + in-LDS IFFT + commutator kernel) and the PFB
+ * arbitrary-rate resampler (f32 timing schedule as a checkpoint table,
+ * re-walked per lane). No CUDA shims, no hipify output.
  *
  * Numerical semantics follow the reference cores (cited per function); the
  * status/consumed/produced math is bit-exact, the float results are
@@ -2509,6 +2510,294 @@ __global__ __launch_bounds__(1024) void k_pfb_synth_fused(
     }
 }
 
+/* ================= PFB arbitrary-rate resampler ======================= *
+ * src/blocks/pfb/arb_resampler.rs. The block's timing state (tau,
+ * base_index, mu, Interpolate/Boundary) is a serial f32 recurrence that
+ * never sees the samples; it decides how many outputs each input yields
+ * and which two filters and mu each output blends. arb_update/arb_step
+ * restate it one reference op per op, round-to-nearest and uncontracted,
+ * shared by the host walk (schedule create, counts) and the device walk,
+ * so both see the same states bit for bit. The recurrence is eventually
+ * periodic, so the host keeps one ArbCk every ARB_Q inputs
+ * over preperiod + period inputs and any stream position folds onto that
+ * table.
+ *
+ * k_pfb_arb: a block owns segments of R = W*RL inputs. Phase 1: lane l <
+ * W seeks input s0 + l*RL (checkpoint + at most ARB_Q-1 silent steps),
+ * then walks its RL inputs and writes one record per output to LDS at
+ * the offset its cumulative output count gives, so the records are
+ * compact along the output index. Phase 2: per channel, the block
+ * stages the segment's samples (plus tpf of history) in LDS and lanes
+ * along the output index compute and store; the walk is paid once for
+ * all channels. The samples of channel c+1 are loaded into registers
+ * while channel c computes (channel 0's during the walk). Staging takes
+ * a block-uniform unguarded path for a segment whose window lies inside
+ * this call's input, a clamped one (carried history in front, zeros
+ * past the end) otherwise. */
+#define ARB_Q 16    /* checkpoint spacing: a seek walks at most 15 inputs */
+#define ARB_CAP 2048 /* output records per segment */
+#define ARB_BLOCK 256
+#define ARB_NV 9     /* staged float2 per lane: R + tpf + 1 <= 9*256 */
+
+struct ArbSt { float tau, mu; unsigned base, bnd; };
+struct ArbCk { float tau, mu; unsigned base, bnd; unsigned long long cum; };
+
+/* One IEEE f32 operation each, never fused with a neighbour. The pragma
+ * is what keeps them apart: the __fadd_rn/__fmul_rn intrinsics are plain
+ * operators in the HIP headers, and under the default -ffp-contract=fast
+ * the multiply in bf = tau*nf fuses with the subtraction in mu = bf -
+ * base into one v_fma_f32, which changes mu. */
+__host__ __device__ static inline float arb_fadd(float a, float b) {
+#pragma clang fp contract(off)
+    return a + b;
+}
+__host__ __device__ static inline float arb_fsub(float a, float b) {
+#pragma clang fp contract(off)
+    return a - b;
+}
+__host__ __device__ static inline float arb_fmul(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
+/* update_timing_state, arb_resampler.rs:132-140. `floor() as usize`
+ * saturates: a negative bf (tau is slightly negative after a Boundary
+ * when delay < 1/nf) and NaN give 0. */
+__host__ __device__ static inline void arb_update(ArbSt& s, float delay,
+                                                  float nff) {
+    s.tau = arb_fadd(s.tau, delay);
+    const float bf = arb_fmul(s.tau, nff);
+    s.base = bf >= 2147483648.f ? 0x7fffffffu
+             : (bf > 0.f ? (unsigned)floorf(bf) : 0u);
+    s.mu = arb_fsub(bf, (float)s.base);
+}
+
+/* consume_single's control flow, :142-188: emit(base_index, boundary, mu)
+ * per output, returns their number. max_out bounds the loop (a rate so
+ * large that tau stops advancing would spin; create refuses those). */
+template <class Emit>
+__host__ __device__ static inline unsigned arb_step(ArbSt& s, unsigned nf,
+                                                    float delay, float nff,
+                                                    unsigned max_out,
+                                                    Emit&& emit) {
+    unsigned cnt = 0;
+    while (s.base < nf && cnt <= max_out) {
+        if (s.bnd) {
+            emit(s.base, 1u, s.mu);
+            cnt++;
+            arb_update(s, delay, nff);
+            s.bnd = 0;
+        } else if (s.base == nf - 1) {
+            s.bnd = 1;
+            s.base = nf;
+        } else {
+            emit(s.base, 0u, s.mu);
+            cnt++;
+            arb_update(s, delay, nff);
+        }
+    }
+    s.tau = arb_fsub(s.tau, 1.0f);
+    s.base -= nf;
+    return cnt;
+}
+
+struct ArbNoEmit {
+    __host__ __device__ void operator()(unsigned, unsigned, float) const {}
+};
+
+/* where fill push k of a tpf-slot window lands, or -1 when a later fill
+ * push overwrites it: WindowBuffer::new(len, false) writes push k at
+ * (start_idx - num_samples_missing) mod len = 2k mod len
+ * (window_buffer.rs:23-32). Odd tpf: 2 is invertible, every push keeps
+ * its slot. Even tpf: only even slots are hit, twice; the second half of
+ * the pushes wins. */
+__host__ __device__ static inline long long arb_fill_slot(long long tpf,
+                                                          long long k) {
+    if ((tpf & 1) == 0 && k < tpf / 2) return -1;
+    return (2 * k) % tpf;
+}
+
+struct ArbParams {
+    const ArbCk* ck;
+    unsigned long long rho, lam, opc, P0, cum0;
+    float delay, nff;
+    unsigned nf, maxo1;
+    int tpf, C, RL, W;
+};
+
+/* fill pushes k0..k0+nfill-1 into the window slots they end up in */
+__global__ void k_pfb_arb_fill(const float2* __restrict__ in,
+                               long long in_stride,
+                               float2* __restrict__ hist, int C, int tpf,
+                               long long k0, long long nfill) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nfill * C) return;
+    const long long c = i / nfill, j = i % nfill;
+    const long long slot = arb_fill_slot(tpf, k0 + j);
+    if (slot >= 0) hist[c * tpf + slot] = in[c * in_stride + j];
+}
+
+/* the window after n more inputs: the last tpf of (old window ++ inputs) */
+__global__ void k_pfb_arb_hist(const float2* __restrict__ in,
+                               long long in_stride, long long n,
+                               const float2* __restrict__ hist_old,
+                               float2* __restrict__ hist_new, int C,
+                               int tpf) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long long)C * tpf) return;
+    const long long c = i / tpf, j = i % tpf;
+    const long long g = n - tpf + j;
+    hist_new[i] = g < 0 ? hist_old[c * tpf + tpf + g] : in[c * in_stride + g];
+}
+
+template <bool TAPS_LDS>
+__global__ __launch_bounds__(ARB_BLOCK) void k_pfb_arb(
+    const float2* __restrict__ in, long long in_stride, long long n,
+    const float2* __restrict__ hist, float2* __restrict__ out,
+    long long out_stride, long long M, const float* __restrict__ rtaps,
+    ArbParams p, long long nseg) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x;
+    const int tpf = p.tpf, R = p.W * p.RL;
+    unsigned* r_i = (unsigned*)smem;
+    unsigned* r_b = r_i + ARB_CAP;
+    float* r_mu = (float*)(r_b + ARB_CAP);
+    unsigned long long* lanecum = (unsigned long long*)(r_mu + ARB_CAP);
+    float2* xs = (float2*)(lanecum + ARB_BLOCK + 2);
+    const float* tp = rtaps;
+    if (TAPS_LDS) {
+        float* tl = (float*)(xs + R + tpf + 1);
+        for (int j = tid; j < (int)p.nf * tpf; j += ARB_BLOCK)
+            tl[j] = rtaps[j];
+        tp = tl; /* first read is behind the segment loop's barriers */
+    }
+    for (long long seg = blockIdx.x; seg < nseg; seg += gridDim.x) {
+        const long long s0 = seg * R;
+        const int len = (int)(n - s0 < R ? n - s0 : R);
+        const int nl = (len + p.RL - 1) / p.RL;
+        /* segment samples: xs[j] is call-relative input s0 - tpf + j, j in
+         * [0, R + tpf]; slot R + tpf is read but never selected. They are
+         * loaded into registers a channel ahead by straight-line clamped
+         * loads (no per-element branch, so one wait serves them all):
+         * unguarded where the segment's window lies inside this call's
+         * input, else carried history in front and zeros past the end. */
+        const bool interior = s0 >= tpf && len == R;
+        const int nv = (R + tpf) / ARB_BLOCK + 1; /* block-uniform */
+        float2 v[ARB_NV];
+#pragma unroll
+        for (int q = 0; q < ARB_NV; q++) v[q] = make_float2(0.f, 0.f);
+        auto stage = [&](int c) {
+            const float2* xc = in + (long long)c * in_stride;
+            if (interior) {
+                const float2* src = xc + (s0 - tpf);
+#pragma unroll
+                for (int q = 0; q < ARB_NV; q++) {
+                    if (q >= nv) break;
+                    const int j = tid + q * ARB_BLOCK;
+                    v[q] = src[j < R + tpf ? j : R + tpf - 1];
+                }
+            } else {
+                const float2* hc = hist + (long long)c * tpf + tpf;
+#pragma unroll
+                for (int q = 0; q < ARB_NV; q++) {
+                    if (q >= nv) break;
+                    const long long g = s0 - tpf + tid + q * ARB_BLOCK;
+                    const float2 x = g < 0 ? hc[g] : xc[g < n ? g : n - 1];
+                    v[q] = g < n ? x : make_float2(0.f, 0.f);
+                }
+            }
+        };
+        stage(0); /* in flight during the walk */
+        /* ---- phase 1: the schedule of this segment ---- */
+        ArbSt st = {0.f, 0.f, 0u, 0u};
+        unsigned long long mycum = 0;
+        if (tid < nl) {
+            const unsigned long long pos =
+                p.P0 + (unsigned long long)s0 + (unsigned)(tid * p.RL);
+            unsigned long long k = 0, fp = pos;
+            if (pos >= p.rho) {
+                k = (pos - p.rho) / p.lam;
+                fp = p.rho + (pos - p.rho) % p.lam;
+            }
+            const ArbCk c = p.ck[fp / ARB_Q];
+            st.tau = c.tau; st.mu = c.mu; st.base = c.base; st.bnd = c.bnd;
+            mycum = c.cum + k * p.opc;
+            const int pre = (int)(fp % ARB_Q);
+            for (int i = 0; i < pre; i++)
+                mycum += arb_step(st, p.nf, p.delay, p.nff, p.maxo1,
+                                  ArbNoEmit());
+            lanecum[tid] = mycum;
+        }
+        __syncthreads();
+        const unsigned long long segcum = lanecum[0];
+        if (tid < nl) {
+            unsigned off = (unsigned)(mycum - segcum);
+            const int first = tid * p.RL;
+            const int cnt = len - first < p.RL ? len - first : p.RL;
+            for (int i = 0; i < cnt; i++) {
+                const unsigned idx = (unsigned)(first + i);
+                arb_step(st, p.nf, p.delay, p.nff, p.maxo1,
+                         [&](unsigned base, unsigned bnd, float mu) {
+                             if (off < ARB_CAP) {
+                                 r_i[off] = idx;
+                                 r_b[off] = base | (bnd << 31);
+                                 r_mu[off] = mu;
+                             }
+                             off++;
+                         });
+            }
+            if (tid == nl - 1) lanecum[ARB_BLOCK] = off;
+        }
+        __syncthreads();
+        const unsigned tot = (unsigned)lanecum[ARB_BLOCK];
+        const int nout = (int)(tot < ARB_CAP ? tot : ARB_CAP);
+        const long long obase = (long long)(segcum - p.cum0);
+        /* ---- phase 2: the outputs, channel by channel ---- */
+        for (int c = 0; c < p.C; c++) {
+#pragma unroll
+            for (int q = 0; q < ARB_NV; q++) {
+                const int j = tid + q * ARB_BLOCK;
+                if (j <= R + tpf) xs[j] = v[q];
+            }
+            __syncthreads();
+            /* the next channel's samples fly while this one computes */
+            if (c + 1 < p.C) stage(c + 1);
+            float2* oc = out + (long long)c * out_stride;
+            /* the records are re-read from LDS per channel: holding a
+             * lane's eight in registers cost 214 VGPRs and two waves per
+             * SIMD */
+            for (int o = tid; o < nout; o += ARB_BLOCK) {
+                const unsigned rbo = r_b[o];
+                /* Interpolate: F[base] and F[base+1] on window i.
+                 * Boundary: F[nf-1] on window i-1, F[0] on window i. */
+                const unsigned bnd = rbo >> 31;
+                const unsigned base = rbo & 0x7fffffffu;
+                const float* ta = tp + (size_t)(bnd ? p.nf - 1 : base) * tpf;
+                const float* tb = tp + (size_t)(bnd ? 0u : base + 1) * tpf;
+                const float2* w = xs + r_i[o] + 1 - bnd;
+                float2 y0 = make_float2(0.f, 0.f), y1 = y0;
+                float2 xcur = w[0];
+                for (int t = 0; t < tpf; t++) {
+                    const float2 xnext = w[t + 1];
+                    const float2 x1 = bnd ? xnext : xcur;
+                    const float h0 = ta[t], h1 = tb[t];
+                    y0.x = fmaf(xcur.x, h0, y0.x);
+                    y0.y = fmaf(xcur.y, h0, y0.y);
+                    y1.x = fmaf(x1.x, h1, y1.x);
+                    y1.y = fmaf(x1.y, h1, y1.y);
+                    xcur = xnext;
+                }
+                const float mu = r_mu[o], om = 1.0f - mu;
+                const long long og = obase + o;
+                if (og >= 0 && og < M)
+                    oc[og] = make_float2(fmaf(om, y0.x, mu * y1.x),
+                                         fmaf(om, y0.y, mu * y1.y));
+            }
+            __syncthreads();
+        }
+    }
+}
+
 /* ================= MovingAvg ========================================== *
  * src/blocks/moving_avg.rs:79-118: per-bin EMA over WIDTH-sized frames,
  * emit every `history` frames; avg state lives in HBM (stateful block).
@@ -3053,7 +3342,7 @@ static fsdr_filter_result resamp_status(size_t L, size_t M, size_t nt_total,
 
 enum FilterKind { K_FIR_CF32, K_FIR_F32, K_DECIM_CF32, K_RESAMP_CF32,
                   K_FFT_CF32, K_MAG2, K_FIR_CCF32, K_MOVAVG,
-                  K_XLATING, K_PFB, K_PFB_SYNTH };
+                  K_XLATING, K_PFB, K_PFB_SYNTH, K_PFB_ARB };
 
 struct fsdr_filter {
     FilterKind kind;
@@ -3109,6 +3398,13 @@ struct fsdr_filter {
      * IFFT'd frames of steps 0..2tpf-2 for the start-up rows. */
     void* d_early = nullptr;
     size_t d_early_bytes = 0;
+    /* PFB arb resampler: width = channels, history = tpf, d_taps the
+     * reversed partition rpart[f][t] = part[f][tpf-1-t]; arb is the owned
+     * schedule and d_ck its checkpoints on the device. d_hist holds two
+     * channels*tpf window copies, the live one picked by i_state;
+     * pfb_pushes counts consumed inputs, the tpf fill pushes included. */
+    fsdr_pfb_arb_schedule* arb = nullptr;
+    void* d_ck = nullptr;
 };
 
 static int ensure_dev(void** p, size_t* cur, size_t want) {
@@ -3637,6 +3933,323 @@ extern "C" fsdr_filter* fsdr_pfb_synthesizer_create(size_t num_channels,
     return f;
 }
 
+/* ---- PFB arb resampler: host-side schedule --------------------------- */
+
+struct fsdr_pfb_arb_schedule {
+    float rate = 0.f, delay = 0.f, nff = 0.f;
+    unsigned nf = 0;
+    unsigned maxo1 = 0; /* most outputs any one input yields */
+    unsigned long long rho = 0, lam = 0, opc = 0;
+    std::vector<ArbCk> ck; /* state + cumulative outputs every ARB_Q */
+    int RL = 0, W = 0;     /* inputs per lane, lanes per segment */
+};
+
+#define ARB_WALK_CAP (1ull << 25)
+
+static inline bool arb_same(const ArbSt& a, const ArbSt& b) {
+    return memcmp(&a.tau, &b.tau, 4) == 0 && memcmp(&a.mu, &b.mu, 4) == 0 &&
+           a.base == b.base && a.bnd == b.bnd;
+}
+
+extern "C" int fsdr_pfb_arb_schedule_create(float rate, size_t num_filters,
+                                            fsdr_pfb_arb_schedule** out) {
+    if (!out) { set_err("null argument"); return FSDR_ERR_INVALID; }
+    *out = nullptr;
+    if (!(rate > 0.f)) {
+        set_err("PfbArbResampler: resampling rate must be greater than zero");
+        return FSDR_ERR_INVALID;
+    }
+    if (num_filters == 0) {
+        set_err("PfbArbResampler: number of filter banks must be greater "
+                "than zero");
+        return FSDR_ERR_INVALID;
+    }
+    if (num_filters > (1u << 20) ||
+        !((double)num_filters / (double)rate < 1073741824.0)) {
+        set_err("pfb arb schedule: num_filters must be at most 2^20 and "
+                "num_filters/rate below 2^30");
+        return FSDR_ERR_UNSUPPORTED;
+    }
+    const unsigned nf = (unsigned)num_filters;
+    const float delay = 1.0f / rate, nff = (float)num_filters;
+    unsigned maxo = 0;
+    bool too_many = false;
+    auto step = [&](ArbSt& s) {
+        const unsigned c = arb_step(s, nf, delay, nff, ARB_CAP, ArbNoEmit());
+        if (c > maxo) maxo = c;
+        if (c > ARB_CAP) too_many = true;
+        return c;
+    };
+    const char* e_out = "pfb arb schedule: one input yields more than 2048 "
+                        "outputs";
+    const char* e_long = "pfb arb schedule: preperiod + period exceed 2^25 "
+                         "inputs";
+    /* Brent: the period lam, then the preperiod rho */
+    const ArbSt s0 = {0.f, 0.f, 0u, 0u};
+    ArbSt tort = s0, hare = s0;
+    step(hare);
+    unsigned long long power = 1, lam = 1;
+    while (!arb_same(tort, hare)) {
+        if (too_many) { set_err(e_out); return FSDR_ERR_UNSUPPORTED; }
+        if (power == lam) {
+            if (power > ARB_WALK_CAP) {
+                set_err(e_long);
+                return FSDR_ERR_UNSUPPORTED;
+            }
+            tort = hare;
+            power *= 2;
+            lam = 0;
+        }
+        step(hare);
+        lam++;
+    }
+    if (too_many) { set_err(e_out); return FSDR_ERR_UNSUPPORTED; }
+    tort = hare = s0;
+    for (unsigned long long i = 0; i < lam; i++) step(hare);
+    unsigned long long rho = 0;
+    while (!arb_same(tort, hare)) {
+        step(tort);
+        step(hare);
+        if (++rho > ARB_WALK_CAP) {
+            set_err(e_long);
+            return FSDR_ERR_UNSUPPORTED;
+        }
+    }
+    if (rho + lam > ARB_WALK_CAP) {
+        set_err(e_long);
+        return FSDR_ERR_UNSUPPORTED;
+    }
+    fsdr_pfb_arb_schedule* s = new fsdr_pfb_arb_schedule();
+    s->rate = rate; s->delay = delay; s->nff = nff; s->nf = nf;
+    s->rho = rho; s->lam = lam;
+    s->ck.reserve((rho + lam + ARB_Q - 1) / ARB_Q);
+    ArbSt st = s0;
+    unsigned long long cum = 0, cum_rho = 0;
+    for (unsigned long long i = 0; i < rho + lam; i++) {
+        if (i % ARB_Q == 0)
+            s->ck.push_back({st.tau, st.mu, st.base, st.bnd, cum});
+        if (i == rho) cum_rho = cum;
+        cum += step(st);
+    }
+    s->opc = cum - cum_rho;
+    s->maxo1 = maxo < 1 ? 1 : maxo;
+    /* segment shape: a lane walks RL inputs (8, fewer where one lane's
+     * outputs alone would pass ARB_CAP), W lanes per segment so that its
+     * outputs fit ARB_CAP whatever the position */
+    s->RL = 8;
+    if ((unsigned)s->RL * s->maxo1 > ARB_CAP) s->RL = ARB_CAP / s->maxo1;
+    s->W = (int)std::min<unsigned>(ARB_BLOCK,
+                                   ARB_CAP / ((unsigned)s->RL * s->maxo1));
+    *out = s;
+    return FSDR_OK;
+}
+
+extern "C" void fsdr_pfb_arb_schedule_destroy(fsdr_pfb_arb_schedule* s) {
+    delete s;
+}
+
+extern "C" int fsdr_pfb_arb_schedule_info(const fsdr_pfb_arb_schedule* s,
+                                          uint64_t* preperiod,
+                                          uint64_t* period,
+                                          uint64_t* outputs_per_period,
+                                          size_t* checkpoint_spacing,
+                                          size_t* segment_inputs) {
+    if (!s) { set_err("null schedule"); return FSDR_ERR_INVALID; }
+    if (preperiod) *preperiod = s->rho;
+    if (period) *period = s->lam;
+    if (outputs_per_period) *outputs_per_period = s->opc;
+    if (checkpoint_spacing) *checkpoint_spacing = ARB_Q;
+    if (segment_inputs) *segment_inputs = (size_t)s->W * s->RL;
+    return FSDR_OK;
+}
+
+/* state in front of input `pos` (pushes after the fill) and the outputs
+ * of the inputs before it: fold onto the table, then < ARB_Q steps */
+static unsigned long long arb_seek(const fsdr_pfb_arb_schedule* s,
+                                   unsigned long long pos, ArbSt* st) {
+    unsigned long long k = 0, fp = pos;
+    if (pos >= s->rho) {
+        k = (pos - s->rho) / s->lam;
+        fp = s->rho + (pos - s->rho) % s->lam;
+    }
+    const ArbCk& c = s->ck[fp / ARB_Q];
+    st->tau = c.tau; st->mu = c.mu; st->base = c.base; st->bnd = c.bnd;
+    unsigned long long cum = c.cum + k * s->opc;
+    for (unsigned i = 0; i < fp % ARB_Q; i++)
+        cum += arb_step(*st, s->nf, s->delay, s->nff, s->maxo1, ArbNoEmit());
+    return cum;
+}
+
+extern "C" uint64_t fsdr_pfb_arb_schedule_count(
+    const fsdr_pfb_arb_schedule* s, uint64_t pushes_after_fill,
+    uint64_t n_inputs) {
+    if (!s) return 0;
+    ArbSt st;
+    return arb_seek(s, pushes_after_fill + n_inputs, &st) -
+           arb_seek(s, pushes_after_fill, &st);
+}
+
+extern "C" size_t fsdr_pfb_arb_schedule_records(
+    const fsdr_pfb_arb_schedule* s, uint64_t first_input, size_t n_inputs,
+    uint64_t* in_index, uint32_t* base_index, uint8_t* boundary, float* mu,
+    size_t cap) {
+    if (!s) return 0;
+    ArbSt st;
+    arb_seek(s, first_input, &st);
+    size_t k = 0;
+    for (size_t i = 0; i < n_inputs; i++)
+        arb_step(st, s->nf, s->delay, s->nff, s->maxo1,
+                 [&](unsigned base, unsigned bnd, float m) {
+                     if (k < cap) {
+                         if (in_index) in_index[k] = first_input + i;
+                         if (base_index) base_index[k] = base;
+                         if (boundary) boundary[k] = (uint8_t)bnd;
+                         if (mu) mu[k] = m;
+                     }
+                     k++;
+                 });
+    return k;
+}
+
+/* One resampler call: the fill work() (:202-215), then one processing
+ * work() on the rest with n = min(n_in, (usize)(out_cap as f32 / rate))
+ * (:218; `as usize` truncates and saturates). Guard: where those n
+ * inputs would yield more than out_cap, the largest prefix that fits. */
+static void arb_work(const fsdr_pfb_arb_schedule* s, size_t tpf,
+                     unsigned long long pushes, size_t n_in, size_t out_cap,
+                     size_t* fill_out, size_t* n_out, size_t* prod_out) {
+    size_t fill = 0;
+    if (pushes < tpf) fill = std::min<unsigned long long>(tpf - pushes, n_in);
+    size_t n = 0, prod = 0;
+    const size_t rem = n_in - fill;
+    if (pushes + fill >= tpf && rem > 0) {
+        const float q = (float)out_cap / s->rate;
+        size_t lim = 0;
+        if (q >= 18446744073709551616.f) lim = SIZE_MAX;
+        else if (q > 0.f) lim = (size_t)q;
+        n = std::min(rem, lim);
+        const unsigned long long P = pushes + fill - tpf;
+        prod = fsdr_pfb_arb_schedule_count(s, P, n);
+        if (prod > out_cap) {
+            size_t lo = 0, hi = n; /* count(lo) fits, count(hi) does not */
+            while (hi - lo > 1) {
+                const size_t mid = lo + (hi - lo) / 2;
+                if (fsdr_pfb_arb_schedule_count(s, P, mid) <= out_cap)
+                    lo = mid;
+                else
+                    hi = mid;
+            }
+            n = lo;
+            prod = fsdr_pfb_arb_schedule_count(s, P, n);
+        }
+    }
+    *fill_out = fill; *n_out = n; *prod_out = prod;
+}
+
+extern "C" void fsdr_pfb_arb_schedule_work(const fsdr_pfb_arb_schedule* s,
+                                           size_t taps_per_filter,
+                                           uint64_t pushes, size_t n_in,
+                                           size_t out_cap, size_t* consumed,
+                                           size_t* produced) {
+    size_t fill = 0, n = 0, prod = 0;
+    if (s && taps_per_filter)
+        arb_work(s, taps_per_filter, pushes, n_in, out_cap, &fill, &n, &prod);
+    if (consumed) *consumed = fill + n;
+    if (produced) *produced = prod;
+}
+
+extern "C" void fsdr_pfb_arb_startup_map(size_t taps_per_filter,
+                                         long long* src) {
+    if (!src) return;
+    for (size_t s = 0; s < taps_per_filter; s++) src[s] = -1;
+    for (size_t k = 0; k < taps_per_filter; k++) {
+        const long long slot = arb_fill_slot((long long)taps_per_filter,
+                                             (long long)k);
+        if (slot >= 0) src[slot] = (long long)k;
+    }
+}
+
+/* LDS of k_pfb_arb: records, lane offsets, the staged segment, and the
+ * taps where they fit beside them */
+static size_t pfb_arb_lds(const fsdr_pfb_arb_schedule* s, size_t tpf,
+                          bool* taps_lds) {
+    const size_t R = (size_t)s->W * s->RL;
+    const size_t base = 3 * ARB_CAP * 4 + (ARB_BLOCK + 2) * 8 +
+                        (R + tpf + 1) * 8;
+    const size_t tb = (size_t)s->nf * tpf * 4;
+    *taps_lds = tb <= 16 * 1024 && base + tb <= 64 * 1024;
+    return base + (*taps_lds ? tb : 0);
+}
+
+extern "C" fsdr_filter* fsdr_pfb_arb_resampler_create(float rate,
+                                                      const float* taps,
+                                                      size_t n_taps,
+                                                      size_t num_filters,
+                                                      size_t num_channels) {
+    /* arb_resampler.rs:92-103 */
+    if (!(rate > 0.f)) {
+        set_err("PfbArbResampler: resampling rate must be greater than zero");
+        return nullptr;
+    }
+    if (!taps || n_taps < num_filters) {
+        set_err("PfbArbResampler: prototype filter length must be at least "
+                "num_filters");
+        return nullptr;
+    }
+    if (num_filters == 0) {
+        set_err("PfbArbResampler: number of filter banks must be greater "
+                "than zero");
+        return nullptr;
+    }
+    if (num_channels == 0 || num_channels > 65536) {
+        set_err("pfb arb resampler: num_channels must be in [1,65536]");
+        return nullptr;
+    }
+    fsdr_filter* f = create_common(K_PFB_ARB);
+    if (!f) return nullptr;
+    if (fsdr_pfb_arb_schedule_create(rate, num_filters, &f->arb) != FSDR_OK) {
+        fsdr_filter_destroy(f);
+        return nullptr;
+    }
+    const size_t nf = num_filters, tpf = (n_taps + nf - 1) / nf;
+    bool taps_lds;
+    if ((size_t)f->arb->W * f->arb->RL + tpf + 1 > ARB_NV * ARB_BLOCK ||
+        pfb_arb_lds(f->arb, tpf, &taps_lds) > 64 * 1024) {
+        set_err("pfb arb resampler: taps per filter too long for the LDS "
+                "tile");
+        fsdr_filter_destroy(f);
+        return nullptr;
+    }
+    f->width = num_channels;
+    f->history = tpf;
+    f->n_taps = n_taps;
+    /* partition_filter_taps (utilities.rs:5-25), each part reversed */
+    std::vector<float> rp(nf * tpf, 0.f);
+    for (size_t t = 0; t < n_taps; t++)
+        rp[(t % nf) * tpf + (tpf - 1 - t / nf)] = taps[t];
+    const size_t ckb = f->arb->ck.size() * sizeof(ArbCk);
+    const size_t hb = 2 * num_channels * tpf * 8;
+    if (hipMalloc(&f->d_taps, rp.size() * sizeof(float)) != hipSuccess ||
+        hipMemcpy(f->d_taps, rp.data(), rp.size() * sizeof(float),
+                  hipMemcpyHostToDevice) != hipSuccess ||
+        hipMalloc(&f->d_ck, ckb) != hipSuccess ||
+        hipMemcpy(f->d_ck, f->arb->ck.data(), ckb,
+                  hipMemcpyHostToDevice) != hipSuccess ||
+        hipMalloc(&f->d_hist, hb) != hipSuccess ||
+        hipMemset(f->d_hist, 0, hb) != hipSuccess) {
+        set_err("pfb arb resampler upload failed");
+        fsdr_filter_destroy(f);
+        return nullptr;
+    }
+    f->d_hist_bytes = hb;
+    return f;
+}
+
+extern "C" const fsdr_pfb_arb_schedule* fsdr_pfb_arb_resampler_schedule(
+    const fsdr_filter* f) {
+    return f && f->kind == K_PFB_ARB ? f->arb : nullptr;
+}
+
 extern "C" fsdr_filter* fsdr_moving_avg_create(size_t width,
                                                float decay_factor,
                                                size_t history) {
@@ -3708,6 +4321,8 @@ extern "C" void fsdr_filter_destroy(fsdr_filter* f) {
     if (f->d_scratch) (void)hipFree(f->d_scratch);
     if (f->d_hist) (void)hipFree(f->d_hist);
     if (f->d_early) (void)hipFree(f->d_early);
+    if (f->d_ck) (void)hipFree(f->d_ck);
+    fsdr_pfb_arb_schedule_destroy(f->arb);
     delete f;
 }
 
@@ -4183,6 +4798,18 @@ extern "C" int fsdr_filter_dev(fsdr_filter* f, const void* d_in, size_t n_in,
             set_err("pfb synthesizer uses fsdr_pfb_synthesizer_run_dev "
                     "(multi-input block)");
             return FSDR_ERR_INVALID;
+        case K_PFB_ARB: {
+            if (f->width != 1) {
+                set_err("multi-channel pfb arb resampler uses "
+                        "fsdr_pfb_arb_resampler_run_dev");
+                return FSDR_ERR_INVALID;
+            }
+            /* stateful block: stream semantics, like MovingAvg */
+            r->status = FSDR_BOTH_SUFFICIENT;
+            return fsdr_pfb_arb_resampler_stream_dev(
+                f, d_in, n_in, n_in, d_out, n_out, n_out, stream,
+                &r->consumed, &r->produced);
+        }
         case K_MOVAVG: {
             /* the work() counting loop (consume a frame, emit every
              * history-th one, stop when input or output room runs out)
@@ -4582,6 +5209,133 @@ extern "C" int fsdr_pfb_synthesizer_stream_dev(fsdr_filter* f,
     if (rc) return rc;
     f->i_state = 1 - f->i_state;
     f->pfb_pushes = p + S;
+    return FSDR_OK;
+}
+
+/* ---- PFB arb resampler: launches ------------------------------------- */
+
+/* `fill` window-fill pushes (the stream's pushes k0..) then n processed
+ * inputs from schedule position P0 yielding M outputs per channel, on
+ * the window `hist`; hist_next (nullable) receives the window after the
+ * call. */
+static int pfb_arb_launch(fsdr_filter* f, const float2* d_in,
+                          size_t in_stride, size_t fill, size_t k0, size_t n,
+                          unsigned long long P0, size_t M, float2* d_out,
+                          size_t out_stride, float2* hist, float2* hist_next,
+                          hipStream_t st) {
+    const fsdr_pfb_arb_schedule* s = f->arb;
+    const int C = (int)f->width, tpf = (int)f->history;
+    if (fill) {
+        hipLaunchKernelGGL(k_pfb_arb_fill,
+                           dim3(grid_for((long long)fill * C, 256)),
+                           dim3(256), 0, st, d_in, (long long)in_stride,
+                           hist, C, tpf, (long long)k0, (long long)fill);
+        HIP_TRY(hipGetLastError());
+    }
+    if (n == 0) return FSDR_OK; /* the fill wrote the window in place */
+    const float2* x = d_in + fill;
+    if (M) {
+        ArbSt st0;
+        ArbParams p;
+        p.ck = (const ArbCk*)f->d_ck;
+        p.rho = s->rho; p.lam = s->lam; p.opc = s->opc;
+        p.P0 = P0; p.cum0 = arb_seek(s, P0, &st0);
+        p.delay = s->delay; p.nff = s->nff;
+        p.nf = s->nf; p.maxo1 = s->maxo1;
+        p.tpf = tpf; p.C = C; p.RL = s->RL; p.W = s->W;
+        const long long R = (long long)s->W * s->RL;
+        const long long nseg = ((long long)n + R - 1) / R;
+        const int grid = (int)std::min<long long>(nseg, grid_cap(256 * 8));
+        bool taps_lds;
+        const size_t lds = pfb_arb_lds(s, (size_t)tpf, &taps_lds);
+        if (taps_lds)
+            hipLaunchKernelGGL(k_pfb_arb<true>, dim3(grid), dim3(ARB_BLOCK),
+                               lds, st, x, (long long)in_stride,
+                               (long long)n, (const float2*)hist, d_out,
+                               (long long)out_stride, (long long)M,
+                               (const float*)f->d_taps, p, nseg);
+        else
+            hipLaunchKernelGGL(k_pfb_arb<false>, dim3(grid), dim3(ARB_BLOCK),
+                               lds, st, x, (long long)in_stride,
+                               (long long)n, (const float2*)hist, d_out,
+                               (long long)out_stride, (long long)M,
+                               (const float*)f->d_taps, p, nseg);
+        HIP_TRY(hipGetLastError());
+    }
+    if (hist_next) {
+        hipLaunchKernelGGL(k_pfb_arb_hist,
+                           dim3(grid_for((long long)C * tpf, 256)), dim3(256),
+                           0, st, x, (long long)in_stride, (long long)n,
+                           (const float2*)hist, hist_next, C, tpf);
+        HIP_TRY(hipGetLastError());
+    }
+    return FSDR_OK;
+}
+
+static int pfb_arb_check(const fsdr_filter* f, size_t in_stride,
+                         size_t n_in, size_t out_stride, size_t out_cap) {
+    if (!f || f->kind != K_PFB_ARB) {
+        set_err("not a pfb arb resampler");
+        return FSDR_ERR_INVALID;
+    }
+    if (f->width > 1 && (n_in > in_stride || out_cap > out_stride)) {
+        set_err("pfb arb resampler: n_in_per_chan exceeds in_stride or "
+                "out_cap_per_chan exceeds out_stride");
+        return FSDR_ERR_INVALID;
+    }
+    return FSDR_OK;
+}
+
+extern "C" int fsdr_pfb_arb_resampler_run_dev(
+    fsdr_filter* f, const void* d_in, size_t in_stride, size_t n_in_per_chan,
+    void* d_out, size_t out_stride, size_t out_cap_per_chan, void* stream,
+    size_t* consumed_per_chan, size_t* produced_per_chan) {
+    REQUIRE_GPU();
+    int rc = pfb_arb_check(f, in_stride, n_in_per_chan, out_stride,
+                           out_cap_per_chan);
+    if (rc) return rc;
+    size_t fill, n, M;
+    arb_work(f->arb, f->history, 0, n_in_per_chan, out_cap_per_chan, &fill,
+             &n, &M);
+    if (consumed_per_chan) *consumed_per_chan = fill + n;
+    if (produced_per_chan) *produced_per_chan = M;
+    if (M == 0) return FSDR_OK; /* zero state: nothing to carry */
+    const size_t hb = f->width * f->history * 8;
+    rc = ensure_dev(&f->d_scratch, &f->d_scratch_bytes, hb);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(f->d_scratch, 0, hb, (hipStream_t)stream));
+    return pfb_arb_launch(f, (const float2*)d_in, in_stride, fill, 0, n, 0, M,
+                          (float2*)d_out, out_stride, (float2*)f->d_scratch,
+                          nullptr, (hipStream_t)stream);
+}
+
+/* Streaming: carries the window (the last tpf samples per channel) and
+ * the consumed-input count across calls, so any chunking reproduces the
+ * one-shot stream. Use one stream per filter. */
+extern "C" int fsdr_pfb_arb_resampler_stream_dev(
+    fsdr_filter* f, const void* d_in, size_t in_stride, size_t n_in_per_chan,
+    void* d_out, size_t out_stride, size_t out_cap_per_chan, void* stream,
+    size_t* consumed_per_chan, size_t* produced_per_chan) {
+    REQUIRE_GPU();
+    int rc = pfb_arb_check(f, in_stride, n_in_per_chan, out_stride,
+                           out_cap_per_chan);
+    if (rc) return rc;
+    const size_t tpf = f->history, p = f->pfb_pushes;
+    size_t fill, n, M;
+    arb_work(f->arb, tpf, p, n_in_per_chan, out_cap_per_chan, &fill, &n, &M);
+    if (consumed_per_chan) *consumed_per_chan = fill + n;
+    if (produced_per_chan) *produced_per_chan = M;
+    if (fill + n == 0) return FSDR_OK;
+    const size_t half = f->width * tpf;
+    float2* h_live = (float2*)f->d_hist + f->i_state * half;
+    float2* h_next = (float2*)f->d_hist + (1 - f->i_state) * half;
+    rc = pfb_arb_launch(f, (const float2*)d_in, in_stride, fill, p, n,
+                        p + fill - (n ? tpf : 0), M, (float2*)d_out,
+                        out_stride, h_live, n ? h_next : nullptr,
+                        (hipStream_t)stream);
+    if (rc) return rc;
+    if (n) f->i_state = 1 - f->i_state;
+    f->pfb_pushes = p + fill + n;
     return FSDR_OK;
 }
 

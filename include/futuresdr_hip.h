@@ -236,6 +236,104 @@ int fsdr_pfb_synthesizer_stream_dev(fsdr_filter* f, const void* d_in,
                                     void* stream, size_t* consumed_per_chan,
                                     size_t* produced);
 
+/* PfbArbResampler (src/blocks/pfb/arb_resampler.rs): resamples Complex32
+ * by an arbitrary f32 rate. Per output it interpolates linearly between
+ * two adjacent polyphase filters, (1-mu)*F[a](w) + mu*F[b](w'), with
+ * part[f][j] = taps[f + j*num_filters] (tpf = ceil(n_taps/num_filters)).
+ *
+ * Schedule. Which input yields which outputs, and each output's filter
+ * index and mu, come from the block's f32 timing recurrence
+ * (arb_resampler.rs:132-140,183-186), which never sees the samples. It is
+ * eventually periodic; the schedule object walks preperiod + period
+ * inputs once at create, with the reference's own f32 operations, and
+ * keeps a checkpoint (state + cumulative output count) every
+ * checkpoint_spacing inputs, so any stream position is reached in O(1)
+ * plus at most checkpoint_spacing steps. Host-only, needs no GPU.
+ * Input positions count the pushes AFTER the window fill (the first tpf
+ * inputs of a stream only fill the window, :202-215).
+ *  _create: FSDR_ERR_INVALID for rate <= 0 (or NaN) or num_filters == 0;
+ *    FSDR_ERR_UNSUPPORTED where the walk passes 2^25 inputs, one input
+ *    yields more than 2048 outputs, num_filters > 2^20, or
+ *    num_filters/rate >= 2^30.
+ *  _info: preperiod and period in inputs, outputs per period, checkpoint
+ *    spacing, and segment_inputs, the inputs one block of the kernel owns
+ *    per pass. NULL out-pointers are skipped.
+ *  _count: outputs of n_inputs inputs starting at pushes_after_fill.
+ *  _records: per output of inputs [first_input, first_input + n_inputs):
+ *    the input index, base_index, the Boundary flag (the output spans two
+ *    inputs: filter num_filters-1 on the previous window, filter 0 on
+ *    this one) and mu. Fills up to cap entries of each non-NULL array;
+ *    returns the number of outputs.
+ *  _work: consumed/produced of one resampler call (below) by a stream
+ *    that has consumed `pushes` inputs in all, for taps_per_filter.
+ *  fsdr_pfb_arb_startup_map: WindowBuffer::new(len, false) puts fill push
+ *    k at slot 2k mod len; src[s] is the push that slot s of the filled
+ *    window holds, -1 for a hole (stays zero). */
+typedef struct fsdr_pfb_arb_schedule fsdr_pfb_arb_schedule;
+int fsdr_pfb_arb_schedule_create(float rate, size_t num_filters,
+                                 fsdr_pfb_arb_schedule** out);
+void fsdr_pfb_arb_schedule_destroy(fsdr_pfb_arb_schedule* s);
+int fsdr_pfb_arb_schedule_info(const fsdr_pfb_arb_schedule* s,
+                               uint64_t* preperiod, uint64_t* period,
+                               uint64_t* outputs_per_period,
+                               size_t* checkpoint_spacing,
+                               size_t* segment_inputs);
+uint64_t fsdr_pfb_arb_schedule_count(const fsdr_pfb_arb_schedule* s,
+                                     uint64_t pushes_after_fill,
+                                     uint64_t n_inputs);
+size_t fsdr_pfb_arb_schedule_records(const fsdr_pfb_arb_schedule* s,
+                                     uint64_t first_input, size_t n_inputs,
+                                     uint64_t* in_index,
+                                     uint32_t* base_index,
+                                     uint8_t* boundary, float* mu,
+                                     size_t cap);
+void fsdr_pfb_arb_schedule_work(const fsdr_pfb_arb_schedule* s,
+                                size_t taps_per_filter, uint64_t pushes,
+                                size_t n_in, size_t out_cap,
+                                size_t* consumed, size_t* produced);
+void fsdr_pfb_arb_startup_map(size_t taps_per_filter, long long* src);
+
+/* The resampler itself, for num_channels >= 1 channels in lockstep (same
+ * rate, taps and stream position, so one schedule serves them all).
+ * _create mirrors the constructor asserts (:92-103: rate > 0, n_taps >=
+ * num_filters, num_filters != 0) as NULL plus an error string, and fails
+ * the same way where the schedule is unsupported or the kernel's LDS tile
+ * cannot hold segment + taps_per_filter samples (taps_per_filter beyond
+ * 255 at the least). Input is channel-major,
+ * in[c*in_stride + t] — the layout fsdr_pfb_channelizer_* writes — and
+ * output is out[c*out_stride + k].
+ * One call is the reference's fill work() followed by one processing
+ * work() on what remains: the first tpf inputs of a stream fill the
+ * window and produce nothing; then n = min(n_in, (size_t)((float)out_cap
+ * / rate)) inputs are processed (:218, f32 division). One deviation: the
+ * call never writes past out_cap_per_chan — if those n inputs would yield
+ * more, the largest prefix that fits is processed instead. Unconsumed
+ * inputs stay with the caller. run_dev = bulk from zero state, leaves the
+ * stream state alone; stream_dev carries the window and the position.
+ * All work is enqueued on `stream` without a host sync. A one-channel
+ * handle also runs through fsdr_filter_dev (stream semantics, status
+ * BOTH_SUFFICIENT) and fsdr_fg_add_filter; with more channels
+ * fsdr_filter_dev returns FSDR_ERR_INVALID. */
+fsdr_filter* fsdr_pfb_arb_resampler_create(float rate, const float* taps,
+                                           size_t n_taps,
+                                           size_t num_filters,
+                                           size_t num_channels);
+const fsdr_pfb_arb_schedule* fsdr_pfb_arb_resampler_schedule(
+    const fsdr_filter* f);
+int fsdr_pfb_arb_resampler_run_dev(fsdr_filter* f, const void* d_in,
+                                   size_t in_stride, size_t n_in_per_chan,
+                                   void* d_out, size_t out_stride,
+                                   size_t out_cap_per_chan, void* stream,
+                                   size_t* consumed_per_chan,
+                                   size_t* produced_per_chan);
+int fsdr_pfb_arb_resampler_stream_dev(fsdr_filter* f, const void* d_in,
+                                      size_t in_stride,
+                                      size_t n_in_per_chan, void* d_out,
+                                      size_t out_stride,
+                                      size_t out_cap_per_chan, void* stream,
+                                      size_t* consumed_per_chan,
+                                      size_t* produced_per_chan);
+
 /* WLAN sync-short autocorrelation helpers (examples/wlan/src/bin/
  * rx.rs:73-96): a*conj(b) Combine and the sliding-SUM MovingAverage
  * (moving_average.rs:65-105; one-shot: len-1 zero items then sums). */

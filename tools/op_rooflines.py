@@ -3,7 +3,8 @@
 XlatingFir (tiled), FirCC (WLAN correlator shape + bulk), resampler
 shapes, the standalone FFT kernel, and the PFB synthesizer (fused and
 staged path per shape, plus the channelizer at the same shape for
-context). Prints TF/s or GB/s vs peak. --synth runs the PFB part only."""
+context). Prints TF/s or GB/s vs peak. --synth runs the PFB synthesizer
+part only, --arb the PFB arbitrary-rate resampler part only."""
 import ctypes
 import os
 import sys
@@ -79,6 +80,71 @@ def pfb_synth_lines(lib, st, d_in, d_out, S, rounds=5):
               f"{tbs:5.2f} TB/s at 16 B/sample")
 
 
+def pfb_arb_lines(lib, st, d_in, S, rounds=5):
+    """PFB arb resampler, S input samples in all per shape: the LoRa shape
+    (rate 2.5, 5 filters, tpf 8) over 64 channels in lockstep, and rate 0.7
+    with 32 filters (tpf 8) on one long channel; for context the rational
+    Resampler(5, 2) with as many taps on the same S samples. `rounds`
+    timings of each, interleaved; median, range and the share of HBM peak
+    at the op's floor of 8 + 8*rate bytes per input sample. Also the
+    create-time schedule walk of the longest cycle found so far."""
+    import time
+    sz = ctypes.c_size_t
+    stream = ctypes.c_void_p(st.cuda_stream)
+    legs = []
+    out_items = int(S * 2.5 * 1.001) + 4096
+    d_out = ctypes.c_void_p()
+    assert lib.fsdr_dev_alloc(ctypes.byref(d_out), out_items * 8) == 0
+    for rate, nf, C in ((2.5, 5, 64), (0.7, 32, 1)):
+        taps = fa.lowpass_kaiser_n(nf * 8, 8.0, 0.5 / nf)
+        rs = fa.PfbArbResampler(rate, taps, nf, C)
+        T = S // C
+        cap = rs.out_cap_for(T)
+        assert C * cap <= out_items
+        cons, prod = sz(), sz()
+
+        def run(rs=rs, T=T, cap=cap, cons=cons, prod=prod):
+            rc = lib.fsdr_pfb_arb_resampler_run_dev(
+                rs._h, d_in, T, T, d_out, cap, cap, stream,
+                ctypes.byref(cons), ctypes.byref(prod))
+            assert rc == 0, lib.fsdr_last_error().decode()
+
+        legs.append((f"pfb_arb(rate={rate},nf={nf},tpf=8,C={C},"
+                     f"T=2^{T.bit_length() - 1})", run, rate,
+                     lambda c=cons, p=prod, T=T: (c.value, p.value, T), rs))
+    rtaps = fa.lowpass_kaiser_n(40, 8.0, 0.1)
+    rr = fa.Resampler(5, 2, rtaps)
+    legs.append(("resampler(5,2,taps=40) context",
+                 lambda: rr.filter_dev(d_in.value, S, d_out.value, out_items,
+                                       stream=st.cuda_stream), 2.5, None, rr))
+    ms = [[] for _ in legs]
+    for _ in range(rounds):
+        for k, leg in enumerate(legs):
+            ms[k].append(timeit(leg[1], reps=5, warm=2))
+    for k, (name, _, rate, counts, _) in enumerate(legs):
+        v = sorted(ms[k])
+        med = v[len(v) // 2]
+        tbs = S * (8 + 8 * rate) / (med * 1e-3) / 1e12
+        extra = ""
+        if counts:
+            c, p, T = counts()
+            assert c == T
+            extra = f"  produced/chan {p}"
+        print(f"{name}: {med:7.3f} ms median of {rounds} "
+              f"[{v[0]:.3f}..{v[-1]:.3f}]  {tbs:5.2f} TB/s at "
+              f"{8 + 8 * rate:.1f} B/input ({tbs / PEAK_HBM:.3f} of HBM "
+              f"peak){extra}")
+    lib.fsdr_dev_free(d_out)
+    for rate, nf in ((0.9371897, 2), (2.5, 5)):
+        t0 = time.perf_counter()
+        s = fa.PfbArbSchedule(rate, nf)
+        dt = time.perf_counter() - t0
+        print(f"pfb_arb schedule create(rate={rate},nf={nf}): {dt:.3f} s on "
+              f"one host core, preperiod {s.preperiod} period {s.period} "
+              f"inputs, one 24-byte checkpoint every {s.checkpoint_spacing}: "
+              f"{-(-(s.preperiod + s.period) // s.checkpoint_spacing) * 24 / 1e6:.2f} MB")
+
+
 def main():
     lib = fa.lib()
     fa.set_device(0)
@@ -90,8 +156,11 @@ def main():
     assert lib.fsdr_dev_alloc(ctypes.byref(d_out), S * 8) == 0
     fa.fill_uniform_dev(d_in.value, S, seed=5, stream=st.cuda_stream)
 
-    if "--synth" in sys.argv[1:]:
-        pfb_synth_lines(lib, st, d_in, d_out, S)
+    if "--synth" in sys.argv[1:] or "--arb" in sys.argv[1:]:
+        if "--synth" in sys.argv[1:]:
+            pfb_synth_lines(lib, st, d_in, d_out, S)
+        if "--arb" in sys.argv[1:]:
+            pfb_arb_lines(lib, st, d_in, S)
         lib.fsdr_dev_free(d_in)
         lib.fsdr_dev_free(d_out)
         return
@@ -130,6 +199,7 @@ def main():
           f"({tbs / PEAK_HBM:.3f} of peak), {tf:5.1f} TF/s")
 
     pfb_synth_lines(lib, st, d_in, d_out, S)
+    pfb_arb_lines(lib, st, d_in, S)
 
     lib.fsdr_dev_free(d_in)
     lib.fsdr_dev_free(d_out)
