@@ -82,6 +82,17 @@ def _load():
     lib.fsdr_decim_fir_cf32_create.argtypes = [sz, f32p, sz]
     lib.fsdr_resamp_cf32_create.restype = vp
     lib.fsdr_resamp_cf32_create.argtypes = [sz, sz, f32p, sz]
+    for fn in (lib.fsdr_resamp_f32_create, lib.fsdr_fm_demod_resamp_create):
+        fn.restype = vp
+        fn.argtypes = [sz, sz, f32p, sz]
+    lib.fsdr_quad_demod_create.restype = vp
+    lib.fsdr_quad_demod_create.argtypes = []
+    lib.fsdr_fm_demod_resamp_fused.restype = ctypes.c_int
+    lib.fsdr_fm_demod_resamp_fused.argtypes = [vp]
+    lib.fsdr_firdes_kaiser_multirate_f32.restype = sz
+    lib.fsdr_firdes_kaiser_multirate_f32.argtypes = [sz, sz, sz,
+                                                     ctypes.c_double, f32p,
+                                                     sz]
     lib.fsdr_fft_cf32_create.restype = vp
     lib.fsdr_fft_cf32_create.argtypes = [sz, ctypes.c_int, ctypes.c_int, f32p]
     lib.fsdr_mag2_create.restype = vp
@@ -438,6 +449,45 @@ class Resampler(Filter):
         self._taps_keep, p = _f32(taps)
         super().__init__(_load().fsdr_resamp_cf32_create(
             interp, decim, p, self._taps_keep.size))
+
+
+class ResamplerF32(Filter):
+    """PolyphaseResamplingFir<f32,f32,f32> —
+    polyphase_resampling_fir.rs:126-141."""
+    ITEM_IN = np.dtype(np.float32)
+    ITEM_OUT = np.dtype(np.float32)
+
+    def __init__(self, interp, decim, taps):
+        self._taps_keep, p = _f32(taps)
+        super().__init__(_load().fsdr_resamp_f32_create(
+            interp, decim, p, self._taps_keep.size))
+
+
+class QuadDemod(Filter):
+    """d[i] = arg(x[i] * conj(x[i-1])), x[-1] carried across calls —
+    the demod Apply of examples/fm-receiver/src/main.rs:99-104."""
+    ITEM_OUT = np.dtype(np.float32)
+
+    def __init__(self):
+        super().__init__(_load().fsdr_quad_demod_create())
+
+
+class FmDemodResampler(Filter):
+    """QuadDemod then ResamplerF32 as one block (Complex32 in, f32 out);
+    the demodulated stream stays on chip when `fused`."""
+    ITEM_OUT = np.dtype(np.float32)
+
+    def __init__(self, interp, decim, taps):
+        self._taps_keep, p = _f32(taps)
+        super().__init__(_load().fsdr_fm_demod_resamp_create(
+            interp, decim, p, self._taps_keep.size))
+
+    @property
+    def fused(self):
+        """True where calls run the fused kernel, False where they
+        demodulate into scratch and run the f32 resampler kernels (span
+        over the LDS budget, or FSDR_FM_FUSED=0). Host-only."""
+        return bool(_load().fsdr_fm_demod_resamp_fused(self._h))
 
 
 class Fft(Filter):
@@ -869,6 +919,21 @@ def kaiser_lowpass(cutoff, transition_bw, max_ripple):
     out = np.zeros(n, np.float32)
     lib.fsdr_firdes_kaiser_lowpass_f32(
         cutoff, transition_bw, max_ripple,
+        out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), out.size)
+    return out
+
+
+def kaiser_multirate(interp, decim, half_len=12, max_ripple=1e-4):
+    """firdes::kaiser::multirate<f32> (basic.rs:412-442), the taps
+    FirBuilder::resampling(interp, decim) designs."""
+    lib = _load()
+    n = lib.fsdr_firdes_kaiser_multirate_f32(interp, decim, half_len,
+                                             max_ripple, None, 0)
+    if n == 0:
+        raise FsdrError(lib.fsdr_last_error().decode())
+    out = np.zeros(n, np.float32)
+    lib.fsdr_firdes_kaiser_multirate_f32(
+        interp, decim, half_len, max_ripple,
         out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), out.size)
     return out
 

@@ -8,7 +8,9 @@
  * Stockham FFT in LDS, the PFB channelizer, the PFB synthesizer (one
  * fused gather + in-LDS IFFT + commutator kernel) and the PFB
  * arbitrary-rate resampler (f32 timing schedule as a checkpoint table,
- * re-walked per lane). No CUDA shims, no hipify output.
+ * re-walked per lane), and the FM receiver back end (quadrature demod
+ * fused into the f32 polyphase resampler's staging pass). No CUDA shims,
+ * no hipify output.
  *
  * Numerical semantics follow the reference cores (cited per function); the
  * status/consumed/produced math is bit-exact, the float results are
@@ -2970,6 +2972,206 @@ __global__ __launch_bounds__(RS_BLOCK) void k_resamp_tiled_cf32(
     }
 }
 
+/* ================= Polyphase resampler, f32 x f32 ===================== *
+ * PolyphaseResamplingFir<f32,f32,f32>, polyphase_resampling_fir.rs:126-141
+ * — the index math of :108-118 on real items. Every f32 resampler kernel
+ * below (naive, tiled, fused FM) forms an output the same way: from 0, t
+ * ascending, one fmaf per tap. An output's bits therefore do not depend
+ * on which kernel, tile or chunk computed it. */
+
+/* Naive kernel (spans over the LDS budget): one output per lane, inputs
+ * via L1/L2. No window passes the caller's n_in (resamp_status). */
+__global__ void k_resamp_f32(const float* __restrict__ in,
+                             float* __restrict__ out,
+                             const float* __restrict__ taps, int n_taps,
+                             int interp, int decim, long long n_out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* s_taps = (float*)smem;
+    for (int i = threadIdx.x; i < n_taps; i += blockDim.x)
+        s_taps[i] = taps[i];
+    __syncthreads();
+    const int tpp = n_taps / interp;
+    long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long k = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+         k < n_out; k += stride) {
+        int bank = (int)((k * decim) % interp);
+        const float* x = in + k * decim / interp;
+        const float* tb = s_taps + bank;
+        float sum = 0.f;
+        for (int t = 0; t < tpp; t++)
+            sum = fmaf(x[t], tb[interp * (tpp - t - 1)], sum);
+        out[k] = sum;
+    }
+}
+
+/* A tile's plane is padded (lds_pad) where decim is even: lane k reads
+ * around k*decim/interp, and a power of two in that stride piles the
+ * lanes onto a few banks. With an odd decim the plain layout is already
+ * spread, and its addresses are base + t: no arithmetic per tap. */
+template <bool PAD>
+__device__ __forceinline__ unsigned rs_at(unsigned e) {
+    return PAD ? lds_pad(e) : e;
+}
+
+/* The dot products of one staged tile: s_x holds the tile's input span,
+ * element 0 = input in_base = out_base*decim / interp, and r0 is that
+ * division's remainder. Output out_base + j then starts (r0 + j*decim) /
+ * interp elements in, on bank (r0 + j*decim) % interp: 32-bit arithmetic
+ * (the host keeps RS_TILE*decim + interp under 2^31). */
+template <bool PAD>
+__device__ __forceinline__ void resamp_tile_dots_f32(
+    const float* s_x, const float* s_taps, float* __restrict__ out,
+    long long out_base, long long n_out, unsigned r0, int interp, int decim,
+    int tpp) {
+#pragma unroll
+    for (int r = 0; r < RS_R; r++) {
+        const unsigned j = threadIdx.x + r * RS_BLOCK;
+        if (out_base + j >= n_out) break;
+        const unsigned num = r0 + j * (unsigned)decim;
+        const unsigned rel = num / (unsigned)interp;
+        const unsigned bank = num - rel * (unsigned)interp;
+        const float* tb = s_taps + bank;
+        float sum = 0.f;
+#pragma unroll 4
+        for (int t = 0; t < tpp; t++)
+            sum = fmaf(s_x[rs_at<PAD>(rel + (unsigned)t)],
+                       tb[interp * (tpp - t - 1)], sum);
+        out[out_base + j] = sum;
+    }
+}
+
+/* LDS-tiled kernel in the shape of k_resamp_tiled_cf32, one plane. */
+template <bool PAD>
+__global__ __launch_bounds__(RS_BLOCK) void k_resamp_tiled_f32(
+    const float* __restrict__ in, float* __restrict__ out,
+    const float* __restrict__ taps, int n_taps, int interp, int decim,
+    long long n_out, long long n_in_valid, int span) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* s_x = (float*)smem;
+    float* s_taps = s_x + plane_floats((unsigned)span);
+    for (int i = threadIdx.x; i < n_taps; i += RS_BLOCK)
+        s_taps[i] = taps[i];
+    const int tpp = n_taps / interp;
+    const long long tiles = (n_out + RS_TILE - 1) / RS_TILE;
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const long long out_base = tile * RS_TILE;
+        const long long in_base = out_base * decim / interp;
+        const unsigned r0 = (unsigned)(out_base * decim - in_base * interp);
+        __syncthreads(); /* previous tile's reads done before restage */
+        for (int i = threadIdx.x; i < span; i += RS_BLOCK) {
+            long long g = in_base + i;
+            s_x[rs_at<PAD>((unsigned)i)] = (g < n_in_valid) ? in[g] : 0.f;
+        }
+        __syncthreads();
+        resamp_tile_dots_f32<PAD>(s_x, s_taps, out, out_base, n_out, r0,
+                                  interp, decim, tpp);
+    }
+}
+
+/* ================= Quadrature demodulator ============================= *
+ * examples/fm-receiver/src/main.rs:99-104: d[i] = arg(x[i]*conj(x[i-1])).
+ * The product as num_complex writes it (Mul for Complex: re = a.re*b.re -
+ * a.im*b.im, im = a.re*b.im + a.im*b.re, with b = conj(p) = (p.re,
+ * -p.im)), every operation rounded on its own: with p = 0+0i, b is
+ * (+0, -0) and the signed zeros reach atan2f as they do in the reference. */
+__device__ __forceinline__ float quad_demod1(float2 a, float2 p) {
+    const float br = p.x, bi = -p.y;
+    const float re = __fsub_rn(__fmul_rn(a.x, br), __fmul_rn(a.y, bi));
+    const float im = __fadd_rn(__fmul_rn(a.x, bi), __fmul_rn(a.y, br));
+    return atan2f(im, re);
+}
+
+/* d[g] for lane-consecutive g, in two steps so that a caller can have
+ * several loads in flight. Load: x[g] in one coalesced access (0 past
+ * n_valid), and on lane 0 of a wave x[g-1], or the carried `last` at the
+ * stream start. Value: every other lane takes x[g-1] from the lane below.
+ * All 64 lanes of a wave call _value together (the shuffle reads the
+ * neighbour's register). */
+struct quad_demod_pair {
+    float2 v, p; /* x[g]; x[g-1], lane 0 only */
+};
+
+__device__ __forceinline__ quad_demod_pair quad_demod_load(
+    const float2* __restrict__ in, const float2* __restrict__ last,
+    long long g, long long n_valid) {
+    quad_demod_pair q;
+    q.v = q.p = make_float2(0.f, 0.f);
+    if (g < n_valid) {
+        q.v = in[g];
+        if ((threadIdx.x & 63) == 0) q.p = g == 0 ? *last : in[g - 1];
+    }
+    return q;
+}
+
+__device__ __forceinline__ float quad_demod_value(quad_demod_pair q,
+                                                  bool valid) {
+    float2 p = make_float2(__shfl_up(q.v.x, 1), __shfl_up(q.v.y, 1));
+    if ((threadIdx.x & 63) == 0) p = q.p;
+    return valid ? quad_demod1(q.v, p) : 0.f;
+}
+
+__global__ __launch_bounds__(256) void k_quad_demod(
+    const float2* __restrict__ in, float* __restrict__ out,
+    const float2* __restrict__ last, long long n) {
+    /* block-uniform trip count: quad_demod_value needs whole waves */
+    for (long long base = blockIdx.x * 256ll; base < n;
+         base += gridDim.x * 256ll) {
+        const long long g = base + threadIdx.x;
+        const float d =
+            quad_demod_value(quad_demod_load(in, last, g, n), g < n);
+        if (g < n) out[g] = d;
+    }
+}
+
+/* Fused quadrature demod + f32 polyphase resampler: k_resamp_tiled_f32
+ * whose staging pass demodulates. A tile loads its Complex32 span once,
+ * writes each d[i] once into the LDS plane (atan2f per input sample, not
+ * per tap) and runs the same dot products; the demodulated stream never
+ * reaches HBM. */
+#define FM_LD 4
+
+template <bool PAD>
+__global__ __launch_bounds__(RS_BLOCK) void k_fm_demod_resamp(
+    const float2* __restrict__ in, float* __restrict__ out,
+    const float* __restrict__ taps, const float2* __restrict__ last,
+    int n_taps, int interp, int decim, long long n_out,
+    long long n_in_valid, int span) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* s_d = (float*)smem;
+    float* s_taps = s_d + plane_floats((unsigned)span);
+    for (int i = threadIdx.x; i < n_taps; i += RS_BLOCK)
+        s_taps[i] = taps[i];
+    const int tpp = n_taps / interp;
+    const long long tiles = (n_out + RS_TILE - 1) / RS_TILE;
+    for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const long long out_base = tile * RS_TILE;
+        const long long in_base = out_base * decim / interp;
+        const unsigned r0 = (unsigned)(out_base * decim - in_base * interp);
+        __syncthreads(); /* previous tile's reads done before restage */
+        /* FM_LD loads of a lane issued together: one round trip to
+         * memory per FM_LD*RS_BLOCK samples, not one per RS_BLOCK */
+        for (int i0 = 0; i0 < span; i0 += FM_LD * RS_BLOCK) {
+            quad_demod_pair q[FM_LD];
+#pragma unroll
+            for (int u = 0; u < FM_LD; u++) {
+                const int i = i0 + u * RS_BLOCK + threadIdx.x;
+                q[u] = quad_demod_load(in, last, in_base + i,
+                                       i < span ? n_in_valid : 0);
+            }
+#pragma unroll
+            for (int u = 0; u < FM_LD; u++) {
+                const int i = i0 + u * RS_BLOCK + threadIdx.x;
+                const float d = quad_demod_value(
+                    q[u], i < span && in_base + i < n_in_valid);
+                if (i < span) s_d[rs_at<PAD>((unsigned)i)] = d;
+            }
+        }
+        __syncthreads();
+        resamp_tile_dots_f32<PAD>(s_d, s_taps, out, out_base, n_out, r0,
+                                  interp, decim, tpp);
+    }
+}
+
 /* ================= FFT: radix-4 Stockham in LDS ======================= *
  * Unnormalized DFT, rustfft convention (forward e^{-2pi i kn/N}) — the
  * reference Fft block's math (src/blocks/fft.rs:190-194). Stockham
@@ -3342,7 +3544,8 @@ static fsdr_filter_result resamp_status(size_t L, size_t M, size_t nt_total,
 
 enum FilterKind { K_FIR_CF32, K_FIR_F32, K_DECIM_CF32, K_RESAMP_CF32,
                   K_FFT_CF32, K_MAG2, K_FIR_CCF32, K_MOVAVG,
-                  K_XLATING, K_PFB, K_PFB_SYNTH, K_PFB_ARB };
+                  K_XLATING, K_PFB, K_PFB_SYNTH, K_PFB_ARB, K_RESAMP_F32,
+                  K_QUAD_DEMOD, K_FM_DEMOD_RESAMP };
 
 struct fsdr_filter {
     FilterKind kind;
@@ -3405,6 +3608,8 @@ struct fsdr_filter {
      * pfb_pushes counts consumed inputs, the tpf fill pushes included. */
     fsdr_pfb_arb_schedule* arb = nullptr;
     void* d_ck = nullptr;
+    /* QuadDemod / FM demod+resampler: d_hist is the one carried Complex32
+     * `last` (main.rs:99-104), zero on a fresh handle. */
 };
 
 static int ensure_dev(void** p, size_t* cur, size_t want) {
@@ -3619,6 +3824,78 @@ extern "C" fsdr_filter* fsdr_resamp_cf32_create(size_t interp, size_t decim,
      * kernel with the input pointer rebased (launch site). */
     if (interp == 1 && decim == 4 && n_taps <= 512)
         f->sub = fsdr_decim_fir_cf32_create(4, taps, n_taps);
+    return f;
+}
+
+/* The f32-items polyphase handles: argument check (decided before a GPU
+ * is needed), then the taps upload. */
+static fsdr_filter* resamp_f32_like_create(FilterKind kind, size_t interp,
+                                           size_t decim, const float* taps,
+                                           size_t n_taps) {
+    if (!taps || n_taps == 0 || interp == 0 || decim == 0 ||
+        n_taps % interp != 0) {
+        /* polyphase_resampling_fir.rs:54-56 assert */
+        set_err("invalid resampler parameters (n_taps % interp must be 0)");
+        return nullptr;
+    }
+    fsdr_filter* f = create_common(kind);
+    if (!f) return nullptr;
+    f->n_taps = n_taps;
+    f->interp = interp;
+    f->decim = decim;
+    f->item_out = 4;
+    if (hipMalloc(&f->d_taps, n_taps * sizeof(float)) != hipSuccess ||
+        hipMemcpy(f->d_taps, taps, n_taps * sizeof(float),
+                  hipMemcpyHostToDevice) != hipSuccess) {
+        set_err("taps upload failed");
+        fsdr_filter_destroy(f);
+        return nullptr;
+    }
+    f->n_taps_padded = (int)n_taps;
+    return f;
+}
+
+extern "C" fsdr_filter* fsdr_resamp_f32_create(size_t interp, size_t decim,
+                                               const float* taps,
+                                               size_t n_taps) {
+    fsdr_filter* f =
+        resamp_f32_like_create(K_RESAMP_F32, interp, decim, taps, n_taps);
+    if (f) f->item_in = 4;
+    return f;
+}
+
+/* the carried `last` of the demodulator, (0, 0) on a fresh handle */
+static bool alloc_demod_last(fsdr_filter* f) {
+    if (ensure_dev(&f->d_hist, &f->d_hist_bytes, sizeof(float2)) != FSDR_OK ||
+        hipMemset(f->d_hist, 0, sizeof(float2)) != hipSuccess) {
+        set_err("demodulator state alloc failed");
+        return false;
+    }
+    return true;
+}
+
+extern "C" fsdr_filter* fsdr_quad_demod_create(void) {
+    fsdr_filter* f = create_common(K_QUAD_DEMOD);
+    if (!f) return nullptr;
+    f->item_out = 4;
+    f->n_taps = 1; /* length(): an Apply block needs one item */
+    if (!alloc_demod_last(f)) {
+        fsdr_filter_destroy(f);
+        return nullptr;
+    }
+    return f;
+}
+
+extern "C" fsdr_filter* fsdr_fm_demod_resamp_create(size_t interp,
+                                                    size_t decim,
+                                                    const float* taps,
+                                                    size_t n_taps) {
+    fsdr_filter* f = resamp_f32_like_create(K_FM_DEMOD_RESAMP, interp, decim,
+                                            taps, n_taps);
+    if (f && !alloc_demod_last(f)) {
+        fsdr_filter_destroy(f);
+        return nullptr;
+    }
     return f;
 }
 
@@ -4651,6 +4928,110 @@ extern "C" int fsdr_fft_bulk_dev(fsdr_filter* f, const void* d_in,
                       (float*)d_mag);
 }
 
+/* ---- f32 resampler / FM back end: launches --------------------------- */
+
+/* Input span of one RS_TILE-output tile, and whether one padded f32 plane
+ * of it plus the taps fits the 64 KiB the tiled kernels ask for. */
+static bool resamp_f32_tile(const fsdr_filter* f, int* span, size_t* lds) {
+    const size_t tpp = f->n_taps / f->interp;
+    const size_t s = (size_t)(RS_TILE - 1) * f->decim / f->interp + tpp + 2;
+    if (s > (1u << 20) || f->n_taps > (1u << 20) || f->decim > (1u << 21))
+        return false; /* also keeps the kernels' 32-bit tile indices exact */
+    *span = (int)s;
+    *lds = ((size_t)plane_floats((unsigned)s) + f->n_taps) * sizeof(float);
+    return *lds <= 64 * 1024;
+}
+
+static int launch_resamp_f32(const fsdr_filter* f, const float* d_in,
+                             float* d_out, size_t produced, size_t n_in,
+                             hipStream_t st) {
+    if (produced == 0) return FSDR_OK;
+    int span = 0;
+    size_t lds_t = 0;
+    const char* rt = getenv("FSDR_RESAMP_TILED");
+    if (resamp_f32_tile(f, &span, &lds_t) && (!rt || atoi(rt) != 0)) {
+        long long tiles = ((long long)produced + RS_TILE - 1) / RS_TILE;
+        int grid = (int)std::min<long long>(tiles, grid_cap(256 * 64));
+        auto kern = f->decim % 2 ? k_resamp_tiled_f32<false>
+                                 : k_resamp_tiled_f32<true>;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(RS_BLOCK),
+                           lds_t, st, d_in, d_out, f->d_taps, (int)f->n_taps,
+                           (int)f->interp, (int)f->decim,
+                           (long long)produced, (long long)n_in, span);
+        HIP_TRY(hipGetLastError());
+        return FSDR_OK;
+    }
+    hipLaunchKernelGGL(k_resamp_f32,
+                       dim3(grid_for((long long)produced, 256)), dim3(256),
+                       f->n_taps * sizeof(float), st, d_in, d_out, f->d_taps,
+                       (int)f->n_taps, (int)f->interp, (int)f->decim,
+                       (long long)produced);
+    HIP_TRY(hipGetLastError());
+    return FSDR_OK;
+}
+
+/* `last` <- d_in[consumed-1], ordered after the kernel that read it */
+static int update_demod_last(fsdr_filter* f, const void* d_in,
+                             size_t consumed, hipStream_t st) {
+    if (consumed == 0) return FSDR_OK;
+    HIP_TRY(hipMemcpyAsync(f->d_hist,
+                           (const float2*)d_in + (consumed - 1),
+                           sizeof(float2), hipMemcpyDeviceToDevice, st));
+    return FSDR_OK;
+}
+
+extern "C" int fsdr_fm_demod_resamp_fused(const fsdr_filter* f) {
+    if (!f || f->kind != K_FM_DEMOD_RESAMP) return 0;
+    int span;
+    size_t lds;
+    const char* e = getenv("FSDR_FM_FUSED");
+    return resamp_f32_tile(f, &span, &lds) && (!e || atoi(e) != 0);
+}
+
+static int launch_fm_demod_resamp(fsdr_filter* f, const void* d_in,
+                                  size_t n_in, void* d_out,
+                                  const fsdr_filter_result* r,
+                                  hipStream_t st) {
+    if (r->produced) {
+        const float2* last = (const float2*)f->d_hist;
+        if (fsdr_fm_demod_resamp_fused(f)) {
+            int span = 0;
+            size_t lds = 0;
+            (void)resamp_f32_tile(f, &span, &lds);
+            long long tiles =
+                ((long long)r->produced + RS_TILE - 1) / RS_TILE;
+            int grid = (int)std::min<long long>(tiles, grid_cap(256 * 64));
+            auto kern = f->decim % 2 ? k_fm_demod_resamp<false>
+                                     : k_fm_demod_resamp<true>;
+            hipLaunchKernelGGL(kern, dim3(grid),
+                               dim3(RS_BLOCK), lds, st, (const float2*)d_in,
+                               (float*)d_out, f->d_taps, last,
+                               (int)f->n_taps, (int)f->interp,
+                               (int)f->decim, (long long)r->produced,
+                               (long long)n_in, span);
+            HIP_TRY(hipGetLastError());
+        } else {
+            /* staged: demodulate what the dot products read, then the
+             * f32 resampler kernels on it */
+            const size_t tpp = f->n_taps / f->interp;
+            const size_t need =
+                (r->produced - 1) * f->decim / f->interp + tpp;
+            int rc = ensure_dev(&f->d_scratch, &f->d_scratch_bytes,
+                                need * sizeof(float));
+            if (rc) return rc;
+            hipLaunchKernelGGL(k_quad_demod,
+                               dim3(grid_for((long long)need, 256)),
+                               dim3(256), 0, st, (const float2*)d_in,
+                               (float*)f->d_scratch, last, (long long)need);
+            HIP_TRY(hipGetLastError());
+            rc = launch_resamp_f32(f, (const float*)f->d_scratch,
+                                   (float*)d_out, r->produced, need, st);
+            if (rc) return rc;
+        }
+    }
+    return update_demod_last(f, d_in, r->consumed, st);
+}
+
 extern "C" int fsdr_filter_dev(fsdr_filter* f, const void* d_in, size_t n_in,
                                void* d_out, size_t n_out, void* stream,
                                fsdr_filter_result* r) {
@@ -4863,6 +5244,29 @@ extern "C" int fsdr_filter_dev(fsdr_filter* f, const void* d_in, size_t n_in,
             HIP_TRY(hipGetLastError());
             f->i_state = i;
             return FSDR_OK;
+        }
+        case K_RESAMP_F32: {
+            *r = resamp_status(f->interp, f->decim, f->n_taps, n_in, n_out);
+            return launch_resamp_f32(f, (const float*)d_in, (float*)d_out,
+                                     r->produced, n_in, st);
+        }
+        case K_QUAD_DEMOD: {
+            size_t m = n_in < n_out ? n_in : n_out; /* apply.rs:108 */
+            r->consumed = r->produced = m;
+            r->status = FSDR_BOTH_SUFFICIENT;
+            if (m == 0) return FSDR_OK;
+            hipLaunchKernelGGL(k_quad_demod,
+                               dim3(grid_for((long long)m, 256)), dim3(256),
+                               0, st, (const float2*)d_in, (float*)d_out,
+                               (const float2*)f->d_hist, (long long)m);
+            HIP_TRY(hipGetLastError());
+            return update_demod_last(f, d_in, m, st);
+        }
+        case K_FM_DEMOD_RESAMP: {
+            /* the demodulated stream is as long as the input, so the
+             * resampler's accounting applies to the Complex32 counts */
+            *r = resamp_status(f->interp, f->decim, f->n_taps, n_in, n_out);
+            return launch_fm_demod_resamp(f, d_in, n_in, d_out, r, st);
         }
         case K_MAG2: {
             size_t m = n_in < n_out ? n_in : n_out; /* apply.rs:108 */
@@ -5531,6 +5935,43 @@ extern "C" size_t fsdr_firdes_kaiser_lowpass_f32(double cutoff,
     double omega_c = (2.0 * cutoff + transition_bw) / 2.0; /* basic.rs:319 */
     firdes_lowpass_h(omega_c, win.data(), num_taps, taps.data());
     for (size_t i = 0; i < num_taps; i++) out[i] = (float)taps[i];
+    return num_taps;
+}
+
+/* firdes::kaiser::multirate<f32>, basic.rs:412-442: the Nyquist (L-th
+ * band) filter FirBuilder::resampling designs, 2*half_polyphase_len taps
+ * per polyphase arm. */
+extern "C" size_t fsdr_firdes_kaiser_multirate_f32(size_t interp,
+                                                   size_t decim,
+                                                   size_t half_polyphase_len,
+                                                   double max_ripple,
+                                                   float* out, size_t cap) {
+    if (interp == 0 || decim == 0 || half_polyphase_len == 0) {
+        /* basic.rs:418-423 asserts */
+        set_err("kaiser multirate: interp, decim and half_polyphase_len "
+                "must be greater than 0");
+        return 0;
+    }
+    if (interp == 1 && decim == 1) { /* :424-426 */
+        if (out && cap >= 1) out[0] = 1.0f;
+        return 1;
+    }
+    const size_t band = interp == 1 ? decim : interp; /* :427-430 */
+    if (half_polyphase_len > ((size_t)1 << 28) / band) {
+        set_err("kaiser multirate: more than 2^29 taps");
+        return 0;
+    }
+    const size_t num_taps = 2 * half_polyphase_len * band;
+    if (!out || cap < num_taps) return num_taps;
+    const double beta = fsdr_kaiser_beta(max_ripple);
+    /* window scaled by interp for unit gain (:433-437) */
+    std::vector<double> win(num_taps + 1), taps(num_taps + 1);
+    fsdr_kaiser_window(num_taps + 1, beta, win.data());
+    for (double& w : win) w = (double)interp * w;
+    const double omega_c = 1.0 / (2.0 * (double)std::max(interp, decim));
+    firdes_lowpass_h(omega_c, win.data(), num_taps + 1, taps.data());
+    for (size_t i = 0; i < num_taps; i++) /* :440 truncate */
+        out[i] = (float)taps[i];
     return num_taps;
 }
 

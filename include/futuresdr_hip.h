@@ -98,6 +98,42 @@ fsdr_filter* fsdr_decim_fir_cf32_create(size_t decimation,
  * multiple of interp (polyphase_resampling_fir.rs:54-56 assert). */
 fsdr_filter* fsdr_resamp_cf32_create(size_t interp, size_t decim,
                                      const float* taps, size_t n_taps);
+/* PolyphaseResamplingFir<f32,f32,f32> — polyphase_resampling_fir.rs:
+ * 126-141: the index math (:108-118) and consumed/produced/status
+ * (:90-106) of the Complex32 handle on 4-byte items in and out; same
+ * n_taps % interp assert. The audio resampler of the FM receiver
+ * (examples/fm-receiver/src/main.rs:121-123). Spans that fit run an
+ * LDS-tiled kernel, longer ones a one-output-per-lane kernel
+ * (FSDR_RESAMP_TILED=0 forces the latter). */
+fsdr_filter* fsdr_resamp_f32_create(size_t interp, size_t decim,
+                                    const float* taps, size_t n_taps);
+/* Quadrature demodulator — the stateful Apply<Complex32 -> f32> of
+ * examples/fm-receiver/src/main.rs:99-104: d[i] = arg(x[i]*conj(x[i-1])),
+ * x[-1] the carried `last`, (0,0) on a fresh handle. Counts follow
+ * src/blocks/apply.rs:100-131 (m = min(in,out), consumed == produced == m,
+ * BOTH_SUFFICIENT); length() is 1. `last` lives in device memory and is
+ * updated from d_in[m-1] on the caller's stream after the kernel, with no
+ * host sync (no update when m == 0). The product is formed as num_complex
+ * does, each operation rounded on its own, so the first sample of a stream
+ * (last = 0+0i, conj = (+0,-0)) has the reference's signed-zero result:
+ * +0, -0, +0 or pi by the sign quadrant of x[0]. */
+fsdr_filter* fsdr_quad_demod_create(void);
+/* Fused FM back end, Complex32 in, f32 out: fsdr_quad_demod followed by
+ * fsdr_resamp_f32 on the demodulated stream (main.rs:99-104,121-129,
+ * `demod > resamp2`). consumed/produced/status are the resampler's
+ * (polyphase_resampling_fir.rs:90-106) with consumed counting Complex32
+ * inputs; `last` becomes x[consumed-1] and stays when consumed == 0. The
+ * caller re-presents unconsumed inputs, and since d[i] depends on x[i]
+ * and x[i-1] alone the output stream is that of the two-block flowgraph
+ * under any chunking, bit for bit. One kernel demodulates a tile's input
+ * span into LDS (atan2f once per input sample) and runs the polyphase dot
+ * products from there; where the span exceeds the LDS budget, or with
+ * FSDR_FM_FUSED=0, the handle demodulates into scratch and launches the
+ * f32 resampler kernels. _fused: which of the two a handle takes now
+ * (1 fused; diagnostics/tests; host-only). */
+fsdr_filter* fsdr_fm_demod_resamp_create(size_t interp, size_t decim,
+                                         const float* taps, size_t n_taps);
+int fsdr_fm_demod_resamp_fused(const fsdr_filter* f);
 /* Fft block — pow2 lengths in [4,4096] run the radix-4 Stockham kernel;
  * ANY other length in [2,2048] runs via Bluestein (two pow2 M>=2len-1
  * passes; the reference block is generic over rustfft plan lengths,
@@ -402,6 +438,15 @@ void   fsdr_kaiser_window(size_t len, double beta, double* out);
 size_t fsdr_firdes_kaiser_lowpass_f32(double cutoff, double transition_bw,
                                       double max_ripple, float* out,
                                       size_t cap);
+/* firdes::kaiser::multirate<f32> (basic.rs:412-442), the Nyquist filter
+ * FirBuilder::resampling designs: 2*half_polyphase_len taps per polyphase
+ * arm, one tap (1.0) for interp == decim == 1. Same query convention.
+ * Returns 0 plus an error string where the reference asserts (a zero
+ * interp, decim or half_polyphase_len, :418-423). */
+size_t fsdr_firdes_kaiser_multirate_f32(size_t interp, size_t decim,
+                                        size_t half_polyphase_len,
+                                        double max_ripple, float* out,
+                                        size_t cap);
 /* firdes::lowpass<f32> over a kaiser window of explicit length
  * (basic.rs:25-42 with windows::kaiser) — fixed-length designer used by
  * the bench (127 taps). */
