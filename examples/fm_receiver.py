@@ -5,9 +5,12 @@ at 1 MS/s, its carrier offset from the tuned frequency.
 
     shift (rotator) > resamp1 6/25 (1 MS/s -> 240 kS/s)
                     > demod + resamp2 1/5 (-> 48 kS/s), one fused block
+                    [> de-emphasis, a one-pole IIR at 48 kS/s]
                     > vector sink
 
-The source, the audio sink and a de-emphasis filter are left out."""
+The source and the audio sink are left out. The de-emphasis filter the
+reference wishes for (main.rs:117) is off by default; receive(x,
+deemph_tau=75e-6) appends it."""
 import os
 import sys
 
@@ -32,7 +35,13 @@ def synthesize(n):
     return np.exp(1j * phase).astype(np.complex64)
 
 
-def receive(x):
+def deemph_taps(tau):
+    """(a, b) of y[k] = (1-p) x[k] + p y[k-1], p = exp(-1/(rate*tau))."""
+    p = np.float32(np.exp(-1.0 / (AUDIO_RATE * tau)))
+    return [p], [np.float32(1.0) - p]
+
+
+def receive(x, deemph_tau=None):
     """The flowgraph above; returns the 48 kS/s audio (float32)."""
     shifted, _ = fa.rotator_host(x, -2 * np.pi * OFFSET / FS)
     if_rate = FS * INTERP / DECIM
@@ -43,7 +52,10 @@ def receive(x):
                                      fa.kaiser_multirate(INTERP, DECIM)))
     back = fg.filter(fa.FmDemodResampler(1, AUDIO_MULT, audio_taps))
     snk = fg.vector_sink()
-    fg.connect(src, resamp1, back, snk)
+    blocks = [src, resamp1, back]
+    if deemph_tau is not None:
+        blocks.append(fg.filter(fa.Iir(*deemph_taps(deemph_tau))))
+    fg.connect(*blocks, snk)
     fg.run()
     return fg.sink_data(snk, np.float32)
 

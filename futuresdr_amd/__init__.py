@@ -89,6 +89,24 @@ def _load():
     lib.fsdr_quad_demod_create.argtypes = []
     lib.fsdr_fm_demod_resamp_fused.restype = ctypes.c_int
     lib.fsdr_fm_demod_resamp_fused.argtypes = [vp]
+    szp = ctypes.POINTER(sz)
+    lib.fsdr_iir_plan_create.restype = ctypes.c_int
+    lib.fsdr_iir_plan_create.argtypes = [f32p, sz, ctypes.POINTER(vp)]
+    lib.fsdr_iir_plan_destroy.restype = None
+    lib.fsdr_iir_plan_destroy.argtypes = [vp]
+    lib.fsdr_iir_plan_info.restype = ctypes.c_int
+    lib.fsdr_iir_plan_info.argtypes = [vp, szp, szp, szp, szp]
+    lib.fsdr_iir_plan_tables.restype = ctypes.c_int
+    lib.fsdr_iir_plan_tables.argtypes = [vp, vp, vp, vp]
+    lib.fsdr_iir_count.restype = None
+    lib.fsdr_iir_count.argtypes = [sz, sz, sz, sz, sz, szp, szp, szp,
+                                   ctypes.POINTER(ctypes.c_int)]
+    lib.fsdr_iir_f32_create.restype = vp
+    lib.fsdr_iir_f32_create.argtypes = [f32p, sz, f32p, sz]
+    lib.fsdr_iir_plan_of.restype = vp
+    lib.fsdr_iir_plan_of.argtypes = [vp]
+    lib.fsdr_fg_add_vector_source_f32.restype = ctypes.c_int
+    lib.fsdr_fg_add_vector_source_f32.argtypes = [vp, f32p, sz]
     lib.fsdr_firdes_kaiser_multirate_f32.restype = sz
     lib.fsdr_firdes_kaiser_multirate_f32.argtypes = [sz, sz, sz,
                                                      ctypes.c_double, f32p,
@@ -490,6 +508,88 @@ class FmDemodResampler(Filter):
         return bool(_load().fsdr_fm_demod_resamp_fused(self._h))
 
 
+def iir_count(n_a, n_b, filled, n_in, n_out):
+    """(filled_after, consumed, produced, status) of one IirFilter call
+    whose memory holds `filled` samples (iir.rs:90-177). Needs no GPU."""
+    fa, c, p = (ctypes.c_size_t() for _ in range(3))
+    st = ctypes.c_int()
+    _load().fsdr_iir_count(n_a, n_b, filled, n_in, n_out, ctypes.byref(fa),
+                           ctypes.byref(c), ctypes.byref(p), ctypes.byref(st))
+    return fa.value, c.value, p.value, st.value
+
+
+class IirPlan:
+    """The constant tables of the blocked IIR recurrence for feedback taps
+    `a_taps`: host-only, needs no GPU. Raises FsdrError (with .code) where
+    the taps are out of range or a table entry overflows f32."""
+
+    def __init__(self, a_taps, _borrowed=None):
+        lib = _load()
+        self._own = _borrowed is None
+        self._destroy = lib.fsdr_iir_plan_destroy
+        if self._own:
+            a, p = _f32(a_taps)
+            self.n_a = a.size
+            h = ctypes.c_void_p()
+            rc = lib.fsdr_iir_plan_create(p, a.size, ctypes.byref(h))
+            if rc != OK:
+                err = FsdrError(f"fsdr error {rc}: "
+                                f"{lib.fsdr_last_error().decode()}")
+                err.code = rc
+                raise err
+            self._h = h
+        else:
+            self.n_a = np.asarray(a_taps).size
+            self._h = ctypes.c_void_p(_borrowed)
+
+    def __del__(self):
+        # may run at interpreter exit, after the module globals are gone
+        if getattr(self, "_own", False) and getattr(self, "_h", None):
+            self._destroy(self._h)
+            self._h = None
+
+    def info(self):
+        """(chunk_len L, chunks_per_tile, tile, scan_pass_tiles)."""
+        v = [ctypes.c_size_t() for _ in range(4)]
+        _check(_load().fsdr_iir_plan_info(self._h,
+                                          *(ctypes.byref(x) for x in v)))
+        return tuple(x.value for x in v)
+
+    def tables(self):
+        """(H [L, n_a], chunk_pow [levels, n_a, n_a], tile_pow likewise) in
+        float64 as the plan computed them; the kernels read each entry
+        rounded to float32 once."""
+        L, chunks, _, passes = self.info()
+        n = self.n_a
+        lc, lt = chunks.bit_length() - 1, passes.bit_length() - 1
+        H = np.zeros((L, n), np.float64)
+        pc = np.zeros((lc, n, n), np.float64)
+        pt = np.zeros((lt, n, n), np.float64)
+        _check(_load().fsdr_iir_plan_tables(self._h, _c(H), _c(pc), _c(pt)))
+        return H, pc, pt
+
+
+class Iir(Filter):
+    """IirFilter<f32,f32,_> — futuredsp iir.rs:56-178: stateful, the
+    memory carried on the device across calls."""
+    ITEM_IN = np.dtype(np.float32)
+    ITEM_OUT = np.dtype(np.float32)
+
+    def __init__(self, a_taps, b_taps):
+        self._a_keep, pa = _f32(a_taps)
+        self._b_keep, pb = _f32(b_taps)
+        super().__init__(_load().fsdr_iir_f32_create(
+            pa, self._a_keep.size, pb, self._b_keep.size))
+
+    @property
+    def plan(self):
+        """The handle's own plan (borrowed; keeps the handle alive)."""
+        p = IirPlan(self._a_keep,
+                    _borrowed=_load().fsdr_iir_plan_of(self._h))
+        p._keep = self
+        return p
+
+
 class Fft(Filter):
     def __init__(self, length, inverse=False, fft_shift=False,
                  normalize=None):
@@ -875,6 +975,11 @@ class Flowgraph:
         self._keep.append(data)
         return _load().fsdr_fg_add_vector_source_cf32(
             self._h, ctypes.c_void_p(data.ctypes.data), data.size)
+
+    def vector_source_f32(self, data):
+        data, p = _f32(data)
+        self._keep.append(data)
+        return _load().fsdr_fg_add_vector_source_f32(self._h, p, data.size)
 
     def head(self, n):
         return _load().fsdr_fg_add_head(self._h, n)

@@ -121,6 +121,16 @@ extern "C" int fsdr_fg_add_vector_source_cf32(fsdr_fg* fg,
     return add_block(fg, std::move(b));
 }
 
+/* the same source over 4-byte items, for graphs that start at an f32
+ * block (FirF32, Iir) */
+extern "C" int fsdr_fg_add_vector_source_f32(fsdr_fg* fg, const float* data,
+                                             size_t n) {
+    Block b; b.kind = B_VEC_SRC;
+    b.item_out = sizeof(float);
+    b.vec.assign((const char*)data, (const char*)data + n * sizeof(float));
+    return add_block(fg, std::move(b));
+}
+
 extern "C" int fsdr_fg_add_head(fsdr_fg* fg, unsigned long long n) {
     Block b; b.kind = B_HEAD; b.head_n = n;
     return add_block(fg, std::move(b));

@@ -9,7 +9,9 @@
  * fused gather + in-LDS IFFT + commutator kernel) and the PFB
  * arbitrary-rate resampler (f32 timing schedule as a checkpoint table,
  * re-walked per lane), and the FM receiver back end (quadrature demod
- * fused into the f32 polyphase resampler's staging pass). No CUDA shims,
+ * fused into the f32 polyphase resampler's staging pass), and the IIR
+ * filter as a blocked recurrence (chunks from zero state, end states
+ * combined by doubling scans with constant matrix powers). No CUDA shims,
  * no hipify output.
  *
  * Numerical semantics follow the reference cores (cited per function); the
@@ -3479,6 +3481,313 @@ __global__ void k_fill_uniform_cf32(float2* __restrict__ out, long long n,
     }
 }
 
+/* ================= IIR filter (futuredsp iir.rs:79-178) ================
+ * y[k] = sum_j b[j] x[k+nb-1-j] + sum_q a[q] y[k-1-q] as a blocked linear
+ * recurrence. With the state vector s = (y[k-1], ...,
+ * y[k-na]) one step is s' = A s + e0 * fir[k], A the companion matrix of
+ * a, so a run of outputs from state s is its run from zero state plus the
+ * homogeneous response of s. A lane walks one chunk of IIR_L outputs from
+ * zero state; the chunk end states are combined across the 256 chunks of
+ * a tile by a doubling scan with the constant matrices A^(L*2^d), and the
+ * tile end states across the call likewise with A^(tile*2^d). No block
+ * waits for another: tile states, their scan and the outputs are three
+ * launches.
+ *
+ * Chunk c of a tile belongs to lane c/4 of wave c%4, so scan levels 0 and
+ * 1 (chunk distance 1, 2) cross the waves through LDS and levels 2..7
+ * (distance 4*2^k) are __shfl_up by 2^k inside a wave, where "chunk >=
+ * distance" is exactly "lane >= 2^k". The staged tile is padded by one
+ * float per 64 (IIR_POS), which makes the lanes' chunk walks (stride 64
+ * floats) and the coalesced staging/store passes both conflict-free. */
+#define IIR_BLOCK 256
+#define IIR_L 16                    /* outputs per chunk */
+#define IIR_C 256                   /* chunks per tile: one per lane */
+#define IIR_TILE (IIR_L * IIR_C)    /* 4096 outputs */
+#define IIR_LEVELS 8                /* log2(IIR_C) */
+#define IIR_P 1024                  /* tile states per pass of the scan */
+#define IIR_P_LEVELS 10             /* log2(IIR_P) */
+#define IIR_NA_MAX 8
+#define IIR_NB_MAX 64
+#define IIR_POS(s) ((s) + ((s) >> 6))
+#define IIR_XS_FLOATS (IIR_POS(IIR_TILE + IIR_NB_MAX - 1) + 1)
+
+struct IirA { float a[IIR_NA_MAX]; };
+
+/* thread -> chunk of the tile (or tile state of the pass), and back, in a
+ * block of W waves: element c belongs to lane c/W of wave c%W */
+template <int W = IIR_BLOCK / 64>
+__device__ __forceinline__ int iir_chunk_of(int tid) {
+    return (tid & 63) * W + (tid >> 6);
+}
+template <int W = IIR_BLOCK / 64>
+__device__ __forceinline__ int iir_tid_of(int c) {
+    return (c % W) * 64 + c / W;
+}
+
+/* p += M o, M row-major NA x NA (block-uniform, so scalar loads) */
+template <int NA>
+__device__ __forceinline__ void iir_matvec_add(float (&p)[NA],
+                                               const float (&o)[NA],
+                                               const float* __restrict__ M) {
+#pragma unroll
+    for (int q = 0; q < NA; q++) {
+        float acc = p[q];
+#pragma unroll
+        for (int r = 0; r < NA; r++) acc = fmaf(M[q * NA + r], o[r], acc);
+        p[q] = acc;
+    }
+}
+
+/* Inclusive doubling scan over the NT states of a block of NT threads:
+ * P_c = sum_{k<=c} B^(c-k) p_k with pw[d] = B^(2^d). The first log2(NT/64)
+ * levels cross the waves through sc (NA*NT floats), the rest are shuffles. */
+template <int NA, int NT = IIR_BLOCK>
+__device__ __forceinline__ void iir_scan(float (&p)[NA],
+                                         const float* __restrict__ pw,
+                                         float* sc) {
+    constexpr int W = NT / 64;
+    constexpr int LW = W == 4 ? 2 : 4, LV = LW + 6;
+    static_assert((1 << LW) == W, "4 or 16 waves");
+    const int tid = threadIdx.x, c = iir_chunk_of<W>(tid), lane = tid & 63;
+    float o[NA];
+#pragma unroll
+    for (int d = 0; d < LW; d++) {
+#pragma unroll
+        for (int r = 0; r < NA; r++) sc[r * NT + tid] = p[r];
+        __syncthreads();
+        const int src = iir_tid_of<W>(c >= (1 << d) ? c - (1 << d) : 0);
+#pragma unroll
+        for (int r = 0; r < NA; r++) o[r] = sc[r * NT + src];
+        __syncthreads();
+        if (c >= (1 << d)) iir_matvec_add<NA>(p, o, pw + d * NA * NA);
+    }
+#pragma unroll
+    for (int d = LW; d < LV; d++) {
+#pragma unroll
+        for (int r = 0; r < NA; r++)
+            o[r] = __shfl_up(p[r], 1 << (d - LW), 64);
+        if (lane >= (1 << (d - LW)))
+            iir_matvec_add<NA>(p, o, pw + d * NA * NA);
+    }
+}
+
+/* Stage inputs [base, base + IIR_TILE + nb - 1) of `in` into xs. GUARD:
+ * the boundary tile, zero past n_need; interior tiles issue their 16 (or
+ * 4 wide, when `in` is 16-byte aligned) loads back to back. */
+template <bool GUARD>
+__device__ __forceinline__ void iir_stage(const float* __restrict__ in,
+                                          long long base, long long n_need,
+                                          int nb, float* xs) {
+    const int tid = threadIdx.x;
+    const float* src = in + base;
+    float t = 0.f;
+    const bool tail = tid < nb - 1;
+    if (GUARD) {
+        const long long left = n_need - base;
+        float v[IIR_L];
+#pragma unroll
+        for (int u = 0; u < IIR_L; u++) {
+            const int s = tid + IIR_BLOCK * u;
+            v[u] = s < left ? src[s] : 0.f;
+        }
+        if (tail && IIR_TILE + tid < left) t = src[IIR_TILE + tid];
+#pragma unroll
+        for (int u = 0; u < IIR_L; u++)
+            xs[IIR_POS(tid + IIR_BLOCK * u)] = v[u];
+    } else if ((((uintptr_t)in) & 15) == 0) {
+        /* IIR_TILE*4 bytes is a multiple of 16: aligned for every tile */
+        float4 v[IIR_L / 4];
+#pragma unroll
+        for (int u = 0; u < IIR_L / 4; u++)
+            v[u] = ((const float4*)src)[tid + IIR_BLOCK * u];
+        if (tail) t = src[IIR_TILE + tid];
+#pragma unroll
+        for (int u = 0; u < IIR_L / 4; u++) {
+            const int p = IIR_POS(4 * (tid + IIR_BLOCK * u));
+            xs[p] = v[u].x; xs[p + 1] = v[u].y;
+            xs[p + 2] = v[u].z; xs[p + 3] = v[u].w;
+        }
+    } else {
+        float v[IIR_L];
+#pragma unroll
+        for (int u = 0; u < IIR_L; u++) v[u] = src[tid + IIR_BLOCK * u];
+        if (tail) t = src[IIR_TILE + tid];
+#pragma unroll
+        for (int u = 0; u < IIR_L; u++)
+            xs[IIR_POS(tid + IIR_BLOCK * u)] = v[u];
+    }
+    if (tail) xs[IIR_POS(IIR_TILE + tid)] = t;
+}
+
+/* The lane's chunk from zero state: z[i] = fir[c0+i] + sum_q a[q] z[i-1-q]
+ * (z[<0] = 0). The FIR part slides a 16-float register window down the
+ * staged tile, one LDS read per tap. */
+template <int NA>
+__device__ __forceinline__ void iir_chunk(const float* xs,
+                                          const float* __restrict__ b,
+                                          int nb, const IirA& a,
+                                          float (&z)[IIR_L]) {
+    const int c0 = iir_chunk_of(threadIdx.x) * IIR_L;
+    float w[IIR_L];
+#pragma unroll
+    for (int i = 0; i < IIR_L; i++) {
+        w[i] = xs[IIR_POS(c0 + nb - 1 + i)];
+        z[i] = 0.f;
+    }
+    for (int j = 0;; j++) {
+        const float bj = b[j];
+#pragma unroll
+        for (int i = 0; i < IIR_L; i++) z[i] = fmaf(bj, w[i], z[i]);
+        if (j + 1 == nb) break;
+#pragma unroll
+        for (int i = IIR_L - 1; i > 0; i--) w[i] = w[i - 1];
+        w[0] = xs[IIR_POS(c0 + nb - 2 - j)];
+    }
+#pragma unroll
+    for (int i = 0; i < IIR_L; i++) {
+        float acc = z[i];
+#pragma unroll
+        for (int q = 0; q < NA; q++)
+            if (i - 1 - q >= 0) acc = fmaf(a.a[q], z[i - 1 - q], acc);
+        z[i] = acc;
+    }
+}
+
+/* Zero-state end state of every tile but the call's last (all of them
+ * full, so there is no boundary here): T[tile*NA + q]. Writes nothing
+ * else. */
+template <int NA>
+__global__ __launch_bounds__(IIR_BLOCK) void k_iir_tile_state(
+    const float* __restrict__ in, float* __restrict__ T,
+    const float* __restrict__ b, int nb, IirA a,
+    const float* __restrict__ pc, long long n_tiles) {
+    __shared__ float xs[IIR_XS_FLOATS];
+    __shared__ float sc[NA * IIR_BLOCK];
+    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        iir_stage<false>(in, tile * IIR_TILE, 0, nb, xs);
+        __syncthreads();
+        float z[IIR_L];
+        iir_chunk<NA>(xs, b, nb, a, z);
+        float p[NA];
+#pragma unroll
+        for (int q = 0; q < NA; q++) p[q] = z[IIR_L - 1 - q];
+        iir_scan<NA>(p, pc, sc);
+        if (threadIdx.x == IIR_BLOCK - 1) {
+#pragma unroll
+            for (int q = 0; q < NA; q++) T[tile * NA + q] = p[q];
+        }
+        __syncthreads(); /* xs is restaged next */
+    }
+}
+
+/* S[k] = state entering tile k: S[0] = mem, S[k+1] = A^tile S[k] + T[k].
+ * One block of IIR_P threads; IIR_P tile states per pass of the doubling
+ * scan, the last state of a pass seeding the next. */
+template <int NA>
+__global__ __launch_bounds__(IIR_P) void k_iir_tile_scan(
+    const float* __restrict__ T, float* __restrict__ S,
+    const float* __restrict__ mem, const float* __restrict__ pt,
+    long long n_tiles) {
+    __shared__ float sc[NA * IIR_P];
+    const int tid = threadIdx.x, c = iir_chunk_of<IIR_P / 64>(tid);
+    float carry[NA];
+#pragma unroll
+    for (int q = 0; q < NA; q++) carry[q] = mem[q];
+    if (tid < NA) S[tid] = mem[tid];
+    for (long long base = 0; base < n_tiles - 1; base += IIR_P) {
+        const long long k = base + c;
+        float p[NA];
+#pragma unroll
+        for (int q = 0; q < NA; q++)
+            p[q] = k < n_tiles - 1 ? T[k * NA + q] : 0.f;
+        if (c == 0) iir_matvec_add<NA>(p, carry, pt);
+        iir_scan<NA, IIR_P>(p, pt, sc);
+        if (k < n_tiles - 1) {
+#pragma unroll
+            for (int q = 0; q < NA; q++) S[(k + 1) * NA + q] = p[q];
+        }
+        if (tid == IIR_P - 1) {
+#pragma unroll
+            for (int q = 0; q < NA; q++) sc[q] = p[q];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q < NA; q++) carry[q] = sc[q];
+        __syncthreads();
+    }
+}
+
+/* The outputs: the chunk pass again, the in-tile scan seeded with the
+ * tile's incoming state S[tile], y = z + H s per chunk, coalesced store
+ * through the staging buffer. The block of the last tile also writes the
+ * memory the next call sees (iir.rs:154-160 after n steps): y[n-1-j], or
+ * where that lies in front of this tile, the incoming state, which for
+ * tile 0 is the old memory shifted (a call with n < na). */
+template <int NA>
+__global__ __launch_bounds__(IIR_BLOCK) void k_iir_apply(
+    const float* __restrict__ in, float* __restrict__ out,
+    const float* __restrict__ S, float* __restrict__ mem_new,
+    const float* __restrict__ b, int nb, IirA a,
+    const float* __restrict__ H, const float* __restrict__ pc, long long n,
+    long long n_tiles) {
+    __shared__ float xs[IIR_XS_FLOATS];
+    __shared__ float sc[(NA ? NA : 1) * IIR_BLOCK];
+    const int tid = threadIdx.x, c = iir_chunk_of(tid);
+    const long long n_need = n + nb - 1;
+    for (long long tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const long long base = tile * IIR_TILE;
+        if (base + IIR_TILE + nb - 1 > n_need)
+            iir_stage<true>(in, base, n_need, nb, xs);
+        else
+            iir_stage<false>(in, base, n_need, nb, xs);
+        __syncthreads();
+        float z[IIR_L];
+        iir_chunk<NA>(xs, b, nb, a, z);
+        if constexpr (NA > 0) {
+            float s_in[NA], p[NA], s[NA];
+#pragma unroll
+            for (int q = 0; q < NA; q++) {
+                s_in[q] = S[tile * NA + q];
+                p[q] = z[IIR_L - 1 - q];
+            }
+            if (c == 0) iir_matvec_add<NA>(p, s_in, pc);
+            iir_scan<NA>(p, pc, sc);
+#pragma unroll
+            for (int q = 0; q < NA; q++) sc[q * IIR_BLOCK + tid] = p[q];
+            __syncthreads();
+            const int src = iir_tid_of(c > 0 ? c - 1 : 0);
+#pragma unroll
+            for (int q = 0; q < NA; q++)
+                s[q] = c > 0 ? sc[q * IIR_BLOCK + src] : s_in[q];
+#pragma unroll
+            for (int i = 0; i < IIR_L; i++) {
+                float corr = 0.f;
+#pragma unroll
+                for (int q = 0; q < NA; q++)
+                    corr = fmaf(H[i * NA + q], s[q], corr);
+                z[i] += corr;
+            }
+        } else {
+            __syncthreads(); /* every lane is done reading xs */
+        }
+#pragma unroll
+        for (int i = 0; i < IIR_L; i++) xs[IIR_POS(c * IIR_L + i)] = z[i];
+        __syncthreads();
+        const long long left = n - base;
+#pragma unroll
+        for (int u = 0; u < IIR_L; u++) {
+            const int s = tid + IIR_BLOCK * u;
+            if (s < left) out[base + s] = xs[IIR_POS(s)];
+        }
+        if (NA > 0 && tile == n_tiles - 1 && tid < NA) {
+            const long long m = n - 1 - tid;
+            mem_new[tid] = m >= base ? xs[IIR_POS((int)(m - base))]
+                                     : S[tile * NA + (base - 1 - m)];
+        }
+        __syncthreads(); /* xs is restaged next */
+    }
+}
+
 /* ================= host-side status math ============================== */
 
 static size_t sat_sub(size_t a, size_t b) { return a > b ? a - b : 0; }
@@ -3545,7 +3854,7 @@ static fsdr_filter_result resamp_status(size_t L, size_t M, size_t nt_total,
 enum FilterKind { K_FIR_CF32, K_FIR_F32, K_DECIM_CF32, K_RESAMP_CF32,
                   K_FFT_CF32, K_MAG2, K_FIR_CCF32, K_MOVAVG,
                   K_XLATING, K_PFB, K_PFB_SYNTH, K_PFB_ARB, K_RESAMP_F32,
-                  K_QUAD_DEMOD, K_FM_DEMOD_RESAMP };
+                  K_QUAD_DEMOD, K_FM_DEMOD_RESAMP, K_IIR_F32 };
 
 struct fsdr_filter {
     FilterKind kind;
@@ -3610,6 +3919,13 @@ struct fsdr_filter {
     void* d_ck = nullptr;
     /* QuadDemod / FM demod+resampler: d_hist is the one carried Complex32
      * `last` (main.rs:99-104), zero on a fresh handle. */
+    /* IIR: d_taps = b, n_taps = nb; iir is the owned plan (a and the
+     * tables) and d_ck the tables on the device (H, chunk powers, tile
+     * powers). d_hist holds two IIR_NA_MAX-float copies of `memory`
+     * (memory[j] = y[-1-j]), the live one picked by i_state; pfb_pushes is
+     * memory.len(), the fill count. d_scratch: tile states, then the
+     * states entering each tile. */
+    fsdr_iir_plan* iir = nullptr;
 };
 
 static int ensure_dev(void** p, size_t* cur, size_t want) {
@@ -4527,6 +4843,167 @@ extern "C" const fsdr_pfb_arb_schedule* fsdr_pfb_arb_resampler_schedule(
     return f && f->kind == K_PFB_ARB ? f->arb : nullptr;
 }
 
+/* ---- IIR plan: the constant matrices of the blocked recurrence -------- */
+
+struct fsdr_iir_plan {
+    int na = 0;
+    std::vector<float> a;
+    /* H[i][q] = (A^(i+1))[0][q], i < IIR_L; pc[d] = A^(IIR_L*2^d) and
+     * pt[d] = A^(IIR_TILE*2^d), d < IIR_P_LEVELS, row-major na x na; all
+     * formed in double (Hd, pcd, ptd: what _tables copies out) and rounded
+     * to f32 once (what the kernels read) */
+    std::vector<double> Hd, pcd, ptd;
+    std::vector<float> H, pc, pt;
+};
+
+extern "C" int fsdr_iir_plan_create(const float* a, size_t n_a,
+                                    fsdr_iir_plan** out) {
+    if (!out) { set_err("null argument"); return FSDR_ERR_INVALID; }
+    *out = nullptr;
+    if (n_a > IIR_NA_MAX || (n_a && !a)) {
+        set_err("iir: n_a must be in [0,8]");
+        return FSDR_ERR_INVALID;
+    }
+    const int na = (int)n_a;
+    typedef std::vector<double> Mat;
+    auto mul = [na](const Mat& x, const Mat& y) {
+        Mat z((size_t)na * na, 0.0);
+        for (int i = 0; i < na; i++)
+            for (int k = 0; k < na; k++)
+                for (int j = 0; j < na; j++)
+                    z[i * na + j] += x[i * na + k] * y[k * na + j];
+        return z;
+    };
+    fsdr_iir_plan* p = new fsdr_iir_plan();
+    p->na = na;
+    p->a.assign(a, a + n_a);
+    bool finite = true;
+    auto put = [&finite](std::vector<double>& dd, std::vector<float>& df,
+                         const double* v, size_t n) {
+        for (size_t i = 0; i < n; i++) {
+            const float f = (float)v[i];
+            if (!std::isfinite(f)) finite = false;
+            dd.push_back(v[i]);
+            df.push_back(f);
+        }
+    };
+    Mat A((size_t)na * na, 0.0);
+    for (int q = 0; q < na; q++) {
+        A[q] = (double)a[q];
+        if (q) A[q * na + q - 1] = 1.0;
+    }
+    Mat M = A;
+    for (int i = 0; i < IIR_L; i++) { /* M = A^(i+1) */
+        put(p->Hd, p->H, M.data(), na);
+        if (i + 1 < IIR_L) M = mul(M, A);
+    }
+    for (int d = 0; d < IIR_LEVELS + IIR_P_LEVELS; d++) {
+        /* M = A^(IIR_L*2^d); IIR_L * 2^IIR_LEVELS is the tile */
+        const bool chunk = d < IIR_LEVELS;
+        put(chunk ? p->pcd : p->ptd, chunk ? p->pc : p->pt, M.data(),
+            (size_t)na * na);
+        M = mul(M, M);
+    }
+    if (!finite) {
+        delete p;
+        set_err("iir: a table entry is not finite in f32 (a pole outside "
+                "the unit circle)");
+        return FSDR_ERR_UNSUPPORTED;
+    }
+    *out = p;
+    return FSDR_OK;
+}
+
+extern "C" void fsdr_iir_plan_destroy(fsdr_iir_plan* p) { delete p; }
+
+extern "C" int fsdr_iir_plan_info(const fsdr_iir_plan* p, size_t* chunk_len,
+                                  size_t* chunks_per_tile, size_t* tile,
+                                  size_t* scan_pass_tiles) {
+    if (!p) { set_err("null plan"); return FSDR_ERR_INVALID; }
+    if (chunk_len) *chunk_len = IIR_L;
+    if (chunks_per_tile) *chunks_per_tile = IIR_C;
+    if (tile) *tile = IIR_TILE;
+    if (scan_pass_tiles) *scan_pass_tiles = IIR_P;
+    return FSDR_OK;
+}
+
+extern "C" int fsdr_iir_plan_tables(const fsdr_iir_plan* p, double* H,
+                                    double* chunk_pow, double* tile_pow) {
+    if (!p) { set_err("null plan"); return FSDR_ERR_INVALID; }
+    if (H) std::copy(p->Hd.begin(), p->Hd.end(), H);
+    if (chunk_pow) std::copy(p->pcd.begin(), p->pcd.end(), chunk_pow);
+    if (tile_pow) std::copy(p->ptd.begin(), p->ptd.end(), tile_pow);
+    return FSDR_OK;
+}
+
+/* iir.rs:90-129,136,166-177: the fill, the counts and the status of one
+ * call by a filter whose memory holds `filled` samples. */
+extern "C" void fsdr_iir_count(size_t n_a, size_t n_b, size_t filled,
+                               size_t n_in, size_t n_out,
+                               size_t* filled_after, size_t* consumed,
+                               size_t* produced, int* status) {
+    const int idle = n_out == 0 ? FSDR_BOTH_SUFFICIENT
+                                : FSDR_INSUFFICIENT_INPUT;
+    size_t m = filled, pushes = 0, n = 0;
+    int st = idle;
+    bool run = n_in != 0;
+    while (run && m < n_a) {
+        if (n_in <= m) { run = false; break; }
+        m++;
+        pushes++;
+    }
+    if (run && pushes == n_in) run = false;
+    if (run) {
+        n = n_in >= n_b ? std::min(n_in - (n_b - 1), n_out) : 0;
+        st = n == n_in && n == n_out ? FSDR_BOTH_SUFFICIENT
+             : n < n_in              ? FSDR_INSUFFICIENT_OUTPUT
+                                     : FSDR_INSUFFICIENT_INPUT;
+    }
+    if (filled_after) *filled_after = n_in ? m : filled;
+    if (consumed) *consumed = n;
+    if (produced) *produced = n;
+    if (status) *status = st;
+}
+
+extern "C" fsdr_filter* fsdr_iir_f32_create(const float* a, size_t n_a,
+                                            const float* b, size_t n_b) {
+    if (!b || n_b == 0 || n_b > IIR_NB_MAX) {
+        /* n_b == 0: iir.rs:132 assert */
+        set_err("iir: n_b must be in [1,64]");
+        return nullptr;
+    }
+    fsdr_iir_plan* plan = nullptr;
+    if (fsdr_iir_plan_create(a, n_a, &plan) != FSDR_OK) return nullptr;
+    fsdr_filter* f = create_common(K_IIR_F32);
+    if (!f) { delete plan; return nullptr; }
+    f->iir = plan;
+    f->n_taps = n_b;
+    f->item_in = f->item_out = 4;
+    std::vector<float> tb(plan->H);
+    tb.insert(tb.end(), plan->pc.begin(), plan->pc.end());
+    tb.insert(tb.end(), plan->pt.begin(), plan->pt.end());
+    const size_t hb = 2 * IIR_NA_MAX * sizeof(float);
+    if (hipMalloc(&f->d_taps, n_b * sizeof(float)) != hipSuccess ||
+        hipMemcpy(f->d_taps, b, n_b * sizeof(float),
+                  hipMemcpyHostToDevice) != hipSuccess ||
+        hipMalloc(&f->d_ck, (tb.size() + 1) * sizeof(float)) != hipSuccess ||
+        (tb.size() &&
+         hipMemcpy(f->d_ck, tb.data(), tb.size() * sizeof(float),
+                   hipMemcpyHostToDevice) != hipSuccess) ||
+        hipMalloc(&f->d_hist, hb) != hipSuccess ||
+        hipMemset(f->d_hist, 0, hb) != hipSuccess) {
+        set_err("iir upload failed");
+        fsdr_filter_destroy(f);
+        return nullptr;
+    }
+    f->d_hist_bytes = hb;
+    return f;
+}
+
+extern "C" const fsdr_iir_plan* fsdr_iir_plan_of(const fsdr_filter* f) {
+    return f && f->kind == K_IIR_F32 ? f->iir : nullptr;
+}
+
 extern "C" fsdr_filter* fsdr_moving_avg_create(size_t width,
                                                float decay_factor,
                                                size_t history) {
@@ -4600,6 +5077,7 @@ extern "C" void fsdr_filter_destroy(fsdr_filter* f) {
     if (f->d_early) (void)hipFree(f->d_early);
     if (f->d_ck) (void)hipFree(f->d_ck);
     fsdr_pfb_arb_schedule_destroy(f->arb);
+    fsdr_iir_plan_destroy(f->iir);
     delete f;
 }
 
@@ -4971,6 +5449,72 @@ static int launch_resamp_f32(const fsdr_filter* f, const float* d_in,
 }
 
 /* `last` <- d_in[consumed-1], ordered after the kernel that read it */
+/* n > 0 outputs of the IIR from the live memory half; the new memory goes
+ * to the other half. Up to three launches (no feedback: one; one tile:
+ * no tile-state pass). */
+template <int NA>
+static int launch_iir_na(fsdr_filter* f, const float* d_in, float* d_out,
+                         long long n, hipStream_t st) {
+    const long long n_tiles = (n + IIR_TILE - 1) / IIR_TILE;
+    const int nb = (int)f->n_taps;
+    const float* b = f->d_taps;
+    IirA a = {};
+    for (int q = 0; q < NA; q++) a.a[q] = f->iir->a[q];
+    const int grid = (int)std::min<long long>(n_tiles, grid_cap(256 * 8));
+    if constexpr (NA == 0) {
+        hipLaunchKernelGGL(k_iir_apply<0>, dim3(grid), dim3(IIR_BLOCK), 0, st,
+                           d_in, d_out, nullptr, nullptr, b, nb, a, nullptr,
+                           nullptr, n, n_tiles);
+        HIP_TRY(hipGetLastError());
+        return FSDR_OK;
+    } else {
+        int rc = ensure_dev(&f->d_scratch, &f->d_scratch_bytes,
+                            (size_t)(2 * n_tiles) * NA * sizeof(float));
+        if (rc) return rc;
+        float* T = (float*)f->d_scratch;
+        float* S = T + n_tiles * NA;
+        const float* H = (const float*)f->d_ck;
+        const float* pc = H + IIR_L * NA;
+        const float* pt = pc + IIR_LEVELS * NA * NA;
+        float* mem = (float*)f->d_hist + f->i_state * IIR_NA_MAX;
+        float* mem_new = (float*)f->d_hist + (f->i_state ^ 1) * IIR_NA_MAX;
+        if (n_tiles > 1) {
+            const int g = (int)std::min<long long>(n_tiles - 1,
+                                                   grid_cap(256 * 8));
+            hipLaunchKernelGGL(k_iir_tile_state<NA>, dim3(g), dim3(IIR_BLOCK),
+                               0, st, d_in, T, b, nb, a, pc, n_tiles - 1);
+            HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_iir_tile_scan<NA>, dim3(1), dim3(IIR_P), 0,
+                           st, (const float*)T, S, (const float*)mem, pt,
+                           n_tiles);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_iir_apply<NA>, dim3(grid), dim3(IIR_BLOCK), 0, st,
+                           d_in, d_out, (const float*)S, mem_new, b, nb, a, H,
+                           pc, n, n_tiles);
+        HIP_TRY(hipGetLastError());
+        f->i_state ^= 1;
+        return FSDR_OK;
+    }
+}
+
+static int launch_iir(fsdr_filter* f, const float* d_in, float* d_out,
+                      long long n, hipStream_t st) {
+    switch (f->iir->na) {
+        case 0: return launch_iir_na<0>(f, d_in, d_out, n, st);
+        case 1: return launch_iir_na<1>(f, d_in, d_out, n, st);
+        case 2: return launch_iir_na<2>(f, d_in, d_out, n, st);
+        case 3: return launch_iir_na<3>(f, d_in, d_out, n, st);
+        case 4: return launch_iir_na<4>(f, d_in, d_out, n, st);
+        case 5: return launch_iir_na<5>(f, d_in, d_out, n, st);
+        case 6: return launch_iir_na<6>(f, d_in, d_out, n, st);
+        case 7: return launch_iir_na<7>(f, d_in, d_out, n, st);
+        case 8: return launch_iir_na<8>(f, d_in, d_out, n, st);
+    }
+    set_err("iir: no kernel for this n_a");
+    return FSDR_ERR_INVALID;
+}
+
 static int update_demod_last(fsdr_filter* f, const void* d_in,
                              size_t consumed, hipStream_t st) {
     if (consumed == 0) return FSDR_OK;
@@ -5267,6 +5811,31 @@ extern "C" int fsdr_filter_dev(fsdr_filter* f, const void* d_in, size_t n_in,
              * resampler's accounting applies to the Complex32 counts */
             *r = resamp_status(f->interp, f->decim, f->n_taps, n_in, n_out);
             return launch_fm_demod_resamp(f, d_in, n_in, d_out, r, st);
+        }
+        case K_IIR_F32: {
+            if (d_in && d_in == d_out) {
+                set_err("iir: in-place call (d_out == d_in)");
+                return FSDR_ERR_INVALID;
+            }
+            const size_t filled = f->pfb_pushes;
+            size_t filled_after;
+            int status;
+            fsdr_iir_count((size_t)f->iir->na, f->n_taps, filled, n_in,
+                           n_out, &filled_after, &r->consumed, &r->produced,
+                           &status);
+            r->status = (fsdr_status)status;
+            if (filled_after > filled) {
+                /* iir.rs:116: memory.push(i[memory.len()]) */
+                float* mem = (float*)f->d_hist + f->i_state * IIR_NA_MAX;
+                HIP_TRY(hipMemcpyAsync(mem + filled,
+                                       (const float*)d_in + filled,
+                                       (filled_after - filled) * sizeof(float),
+                                       hipMemcpyDeviceToDevice, st));
+                f->pfb_pushes = filled_after;
+            }
+            if (r->produced == 0) return FSDR_OK;
+            return launch_iir(f, (const float*)d_in, (float*)d_out,
+                              (long long)r->produced, st);
         }
         case K_MAG2: {
             size_t m = n_in < n_out ? n_in : n_out; /* apply.rs:108 */

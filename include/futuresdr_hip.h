@@ -134,6 +134,67 @@ fsdr_filter* fsdr_quad_demod_create(void);
 fsdr_filter* fsdr_fm_demod_resamp_create(size_t interp, size_t decim,
                                          const float* taps, size_t n_taps);
 int fsdr_fm_demod_resamp_fused(const fsdr_filter* f);
+/* IirFilter<f32,f32,_> — crates/futuredsp/src/iir.rs:56-178, the crate's
+ * one StatefulFilter: y[k] = sum_j b[j]*in[k+n_b-1-j] + sum_j a[j]*y[k-1-j]
+ * with `memory` (memory[j] = y[-1-j]) carried in device memory. One call
+ * is taps_accessor_work (:79-178) literally:
+ *  - n_in == 0 returns (0, 0).
+ *  - While memory holds fewer than n_a samples it is filled from
+ *    in[memory.len()] of this call's input (:102-118); a call whose input
+ *    ends inside the fill, or is no longer than the pushes it made,
+ *    returns (0, 0) and keeps the pushes (:105-129). The fill consumes
+ *    nothing: the first n_a inputs of a stream are both the initial
+ *    "previous outputs" and ordinary inputs. The handle mirrors this with
+ *    a host-side fill count and device-to-device copies.
+ *  - n = n_in >= n_b ? min(n_in - (n_b-1), n_out) : 0 outputs, consumed ==
+ *    produced == n; BOTH_SUFFICIENT if n == n_in == n_out, else
+ *    INSUFFICIENT_OUTPUT if n < n_in (for n_b > 1 every input-limited call;
+ *    the reference's quirk, kept), else INSUFFICIENT_INPUT. A (0, 0) return
+ *    of the first two cases is BOTH_SUFFICIENT for n_out == 0 and
+ *    INSUFFICIENT_INPUT otherwise.
+ *  - memory becomes y[n-1-j] for j < n and the old memory[j-n] beyond: a
+ *    call with n < n_a shifts it. length() is n_b.
+ * fsdr_iir_count is that accounting alone for a memory of `filled`
+ * samples, host-only.
+ * Limits: n_b in [1,64] (n_b == 0 is the reference's assert), n_a in
+ * [0,8] (n_a == 0 is a FIR with these counts); outside, NULL plus an error
+ * string. An in-place call (d_out == d_in) returns FSDR_ERR_INVALID.
+ * The recurrence is run blocked ("IIR"): a lane walks a chunk
+ * of outputs from zero state, chunk end states are combined over a tile,
+ * and tile end states over the call, by doubling scans with constant
+ * powers of the companion matrix A of `a` (first row a, ones below the
+ * diagonal). Results differ from the serial loop by rounding only, inside
+ * the bound tests/iir_ref.py states. All work is enqueued on `stream`
+ * without a host sync; no block waits for another.
+ * The plan holds those constants, computed in double from `a` alone and
+ * rounded to f32 once; host-only, needs no GPU.
+ *  _create: FSDR_ERR_INVALID for n_a > 8; FSDR_ERR_UNSUPPORTED where a
+ *    table entry is not finite in f32, which covers a pole outside the
+ *    unit circle. A deliberate deviation: the reference runs such a filter
+ *    until it overflows. Poles on the unit circle are supported.
+ *  _info: outputs per chunk L, chunks per tile, outputs per tile, and the
+ *    tile states one pass of the tile scan covers (a longer call chains
+ *    passes). NULL out-pointers are skipped.
+ *  _tables: H[i*n_a+q] = (A^(i+1))[0][q] for i < L; chunk_pow[d] =
+ *    A^(L*2^d) for d < log2(chunks per tile); tile_pow[d] = A^(tile*2^d)
+ *    for d < log2(tile states per pass); matrices row-major n_a x n_a.
+ *    The entries are the doubles the plan computed; the kernels read each
+ *    one rounded to f32, i.e. (float)entry. NULL out-pointers are skipped.
+ * fsdr_filter_variant reports zeros for this handle. */
+typedef struct fsdr_iir_plan fsdr_iir_plan;
+int fsdr_iir_plan_create(const float* a, size_t n_a, fsdr_iir_plan** out);
+void fsdr_iir_plan_destroy(fsdr_iir_plan* p);
+int fsdr_iir_plan_info(const fsdr_iir_plan* p, size_t* chunk_len,
+                       size_t* chunks_per_tile, size_t* tile,
+                       size_t* scan_pass_tiles);
+int fsdr_iir_plan_tables(const fsdr_iir_plan* p, double* H,
+                         double* chunk_pow, double* tile_pow);
+void fsdr_iir_count(size_t n_a, size_t n_b, size_t filled, size_t n_in,
+                    size_t n_out, size_t* filled_after, size_t* consumed,
+                    size_t* produced, int* status);
+fsdr_filter* fsdr_iir_f32_create(const float* a, size_t n_a, const float* b,
+                                 size_t n_b);
+const fsdr_iir_plan* fsdr_iir_plan_of(const fsdr_filter* f);
 /* Fft block — pow2 lengths in [4,4096] run the radix-4 Stockham kernel;
  * ANY other length in [2,2048] runs via Bluestein (two pow2 M>=2len-1
  * passes; the reference block is generic over rustfft plan lengths,
@@ -531,6 +592,8 @@ fsdr_fg* fsdr_fg_create(void);
 int  fsdr_fg_add_null_source_cf32(fsdr_fg* fg);
 int  fsdr_fg_add_vector_source_cf32(fsdr_fg* fg, const fsdr_cf32* data,
                                     size_t n);
+int  fsdr_fg_add_vector_source_f32(fsdr_fg* fg, const float* data,
+                                   size_t n);
 int  fsdr_fg_add_head(fsdr_fg* fg, unsigned long long n);
 int  fsdr_fg_add_filter(fsdr_fg* fg, fsdr_filter* f);
 int  fsdr_fg_add_null_sink(fsdr_fg* fg);

@@ -4,7 +4,8 @@ XlatingFir (tiled), FirCC (WLAN correlator shape + bulk), resampler
 shapes, the standalone FFT kernel, and the PFB synthesizer (fused and
 staged path per shape, plus the channelizer at the same shape for
 context). Prints TF/s or GB/s vs peak. --synth runs the PFB synthesizer
-part only, --arb the PFB arbitrary-rate resampler part only."""
+part only, --arb the PFB arbitrary-rate resampler part only, --iir the IIR
+filter part only."""
 import ctypes
 import os
 import sys
@@ -145,6 +146,50 @@ def pfb_arb_lines(lib, st, d_in, S, rounds=5):
               f"{-(-(s.preperiod + s.period) // s.checkpoint_spacing) * 24 / 1e6:.2f} MB")
 
 
+def iir_lines(lib, st, d_in, d_out, S, rounds=5):
+    """IIR filter over S device-resident f32 samples in one call: the
+    de-emphasis one-pole (D), a biquad (B) and an order-8 filter (O) of
+    tests/iir_ref.py; for context a device-to-device copy of the same
+    8 B/sample and FirF32 with as many taps as the biquad has feed-forward
+    taps. `rounds` timings of each (5 back-to-back calls after 2 warm-up
+    calls), the legs interleaved; median, range, and the rate against the
+    op's floor of 8 B/sample and against the 12 B/sample the three-launch
+    design moves (the input is read twice)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(__file__), "..",
+                                    "tests"))
+    import iir_ref
+    legs = []
+    for name in ("D", "B", "O"):
+        a, b = iir_ref.FILTERS[name]
+        f = fa.Iir(a, b)
+        legs.append((f"iir {name} (n_a={a.size}, n_b={b.size})",
+                     lambda f=f: f.filter_dev(d_in.value, S, d_out.value, S,
+                                              stream=st.cuda_stream), f))
+    fir = fa.FirF32(iir_ref.FILTERS["B"][1])
+    legs.append(("fir_f32(3 taps) context",
+                 lambda: fir.filter_dev(d_in.value, S, d_out.value, S,
+                                        stream=st.cuda_stream), fir))
+    src = torch.empty(S, dtype=torch.float32, device="cuda")
+    dst = torch.empty_like(src)
+    legs.append(("d2d copy, 8 B/sample", lambda: dst.copy_(src), None))
+    ms = [[] for _ in legs]
+    for _ in range(rounds):
+        for k, leg in enumerate(legs):
+            ms[k].append(timeit(leg[1], reps=5, warm=2))
+    copy_med = sorted(ms[-1])[rounds // 2]
+    for k, (name, _, _) in enumerate(legs):
+        v = sorted(ms[k])
+        med = v[len(v) // 2]
+        tbs = S * 8 / (med * 1e-3) / 1e12
+        line = (f"{name:26s}: {med:7.3f} ms median of {rounds} "
+                f"[{v[0]:.3f}..{v[-1]:.3f}]  {tbs:5.2f} TB/s at 8 B/sample "
+                f"({tbs / PEAK_HBM:.3f} of HBM peak), "
+                f"{med / copy_med:.2f}x the copy")
+        if name.startswith("iir"):
+            line += f"; {tbs * 1.5:5.2f} TB/s of the 12 B/sample moved"
+        print(line)
+
+
 def main():
     lib = fa.lib()
     fa.set_device(0)
@@ -156,7 +201,9 @@ def main():
     assert lib.fsdr_dev_alloc(ctypes.byref(d_out), S * 8) == 0
     fa.fill_uniform_dev(d_in.value, S, seed=5, stream=st.cuda_stream)
 
-    if "--synth" in sys.argv[1:] or "--arb" in sys.argv[1:]:
+    if {"--synth", "--arb", "--iir"} & set(sys.argv[1:]):
+        if "--iir" in sys.argv[1:]:
+            iir_lines(lib, st, d_in, d_out, S)
         if "--synth" in sys.argv[1:]:
             pfb_synth_lines(lib, st, d_in, d_out, S)
         if "--arb" in sys.argv[1:]:
