@@ -12,6 +12,8 @@ in lockstep through one batched call that reads the channelizer's
 channel-major output buffer as it is (stride out_cap_per_chan). A tone
 placed inside one channel must come out of that channel's resampled stream
 at 1/2.5 of its channel-rate frequency; the script prints where it lands.
+What follows per channel in the reference, fft_demod's dechirp + FFT +
+argmax/LLR on whole symbols, is examples/lora_demod.py.
 
 Run on a box with an MI355X:  python examples/lora_frontend.py
 """

@@ -107,6 +107,19 @@ def _load():
     lib.fsdr_iir_plan_of.argtypes = [vp]
     lib.fsdr_fg_add_vector_source_f32.restype = ctypes.c_int
     lib.fsdr_fg_add_vector_source_f32.argtypes = [vp, f32p, sz]
+    lib.fsdr_lora_demod_create.restype = vp
+    lib.fsdr_lora_demod_create.argtypes = [ctypes.c_uint, ctypes.c_int]
+    lib.fsdr_lora_demod_set_frame.restype = ctypes.c_int
+    lib.fsdr_lora_demod_set_frame.argtypes = [vp, ctypes.c_longlong,
+                                              ctypes.c_double, ctypes.c_int]
+    lib.fsdr_lora_downchirp.restype = ctypes.c_int
+    lib.fsdr_lora_downchirp.argtypes = [ctypes.c_uint, ctypes.c_longlong,
+                                        ctypes.c_double, vp]
+    lib.fsdr_lora_log_i0.restype = ctypes.c_double
+    lib.fsdr_lora_log_i0.argtypes = [ctypes.c_double]
+    lib.fsdr_lora_demod_count.restype = ctypes.c_int
+    lib.fsdr_lora_demod_count.argtypes = [ctypes.c_uint, sz, sz, szp, szp,
+                                          ctypes.POINTER(ctypes.c_int)]
     lib.fsdr_firdes_kaiser_multirate_f32.restype = sz
     lib.fsdr_firdes_kaiser_multirate_f32.argtypes = [sz, sz, sz,
                                                      ctypes.c_double, f32p,
@@ -588,6 +601,69 @@ class Iir(Filter):
                     _borrowed=_load().fsdr_iir_plan_of(self._h))
         p._keep = self
         return p
+
+
+LORA_RAW = 0
+LORA_HARD = 1
+LORA_SOFT = 2
+
+
+def lora_downchirp(sf, cfo_int=0, cfo_frac=0.0):
+    """The HARD/SOFT dechirp table of a LoraFftDemod: conj(build_upchirp(0,
+    sf, 1, false)) (utils.rs:884-914, f32 phase) rotated by the cfo in f64.
+    Needs no GPU."""
+    if not 5 <= sf <= 12:
+        raise FsdrError("lora: sf must be in [5,12]")
+    out = np.zeros(1 << sf, CF32)
+    _check(_load().fsdr_lora_downchirp(sf, cfo_int, cfo_frac, _c(out)))
+    return out
+
+
+def lora_log_i0(x):
+    """ln I0(x) as the SOFT kernel evaluates it. Needs no GPU."""
+    return _load().fsdr_lora_log_i0(float(x))
+
+
+def lora_demod_count(sf, n_in, n_out):
+    """(consumed, produced, status) of one LoraFftDemod call. Needs no
+    GPU."""
+    c, p = ctypes.c_size_t(), ctypes.c_size_t()
+    st = ctypes.c_int()
+    _check(_load().fsdr_lora_demod_count(sf, n_in, n_out, ctypes.byref(c),
+                                         ctypes.byref(p), ctypes.byref(st)))
+    return c.value, p.value, st.value
+
+
+class LoraFftDemod(Filter):
+    """The arithmetic of the reference's FftDemod (examples/lora
+    fft_demod.rs) and of FrameSync's get_symbol_val (utils.rs:1059-1078):
+    dechirp, FFT, |X|^2 and the bin reduction in one kernel. `mode` is
+    LORA_RAW (uint16 argmax, 0xFFFF for zero energy), LORA_HARD (uint16
+    symbol) or LORA_SOFT (float64[12] LLRs per symbol, MSB first)."""
+
+    def __init__(self, sf, mode):
+        self.sf, self.mode = sf, mode
+        self.ITEM_OUT = np.dtype(np.float64 if mode == LORA_SOFT
+                                 else np.uint16)
+        super().__init__(_load().fsdr_lora_demod_create(sf, mode))
+
+    def set_frame(self, cfo_int=0, cfo_frac=0.0, reduced_rate=False):
+        """The frame_info state of fft_demod.rs:355-399; reduced_rate as
+        :72-75 computes it."""
+        _check(_load().fsdr_lora_demod_set_frame(self._h, cfo_int, cfo_frac,
+                                                 int(bool(reduced_rate))))
+
+    def filter(self, inp, n_out):
+        """numpy in -> (y, consumed, produced, status); y is uint16[produced]
+        or float64[produced, 12]."""
+        lib = _load()
+        inp = np.ascontiguousarray(inp, CF32)
+        shape = (n_out, 12) if self.mode == LORA_SOFT else (n_out,)
+        out = np.zeros(shape, self.ITEM_OUT)
+        r = _Result()
+        _check(lib.fsdr_filter_host(self._h, _c(inp), inp.size, _c(out),
+                                    n_out, ctypes.byref(r)))
+        return out[: r.produced], r.consumed, r.produced, r.status
 
 
 class Fft(Filter):

@@ -11,8 +11,9 @@
  * re-walked per lane), and the FM receiver back end (quadrature demod
  * fused into the f32 polyphase resampler's staging pass), and the IIR
  * filter as a blocked recurrence (chunks from zero state, end states
- * combined by doubling scans with constant matrix powers). No CUDA shims,
- * no hipify output.
+ * combined by doubling scans with constant matrix powers), and the LoRa
+ * FFT demodulator (dechirp while staging, in-LDS FFT, argmax or max-log
+ * LLRs reduced per symbol). No CUDA shims, no hipify output.
  *
  * Numerical semantics follow the reference cores (cited per function); the
  * status/consumed/produced math is bit-exact, the float results are
@@ -3788,6 +3789,260 @@ __global__ __launch_bounds__(IIR_BLOCK) void k_iir_apply(
     }
 }
 
+/* ================= LoRa FFT demodulator =================================
+ * One symbol of N = 2^sf samples times the handle's downchirp, N-point
+ * forward FFT, |X|^2 in f32, then one of three reductions over the bins
+ * ("LoRa FFT demodulator"): RAW is get_symbol_val
+ * (examples/lora/src/utils.rs:1059-1078), HARD is fft_demod.rs:115-120 +
+ * 238-248, SOFT the max-log branch of compute_llrs (fft_demod.rs:126-208).
+ * A block of 256 threads holds LORA spb = min(16, max(1, 1024/N)) symbols
+ * in fft_swz ping/pong buffers, 256/spb threads each; the product is
+ * formed while staging, the spectrum never leaves LDS, and a symbol leaves
+ * as one u16 or twelve f64. Blocks walk the batches of spb symbols
+ * persistently. */
+#define LORA_BLOCK 256
+#define LORA_RAW 0
+#define LORA_HARD 1
+#define LORA_SOFT 2
+#define LORA_MAX_SF 12
+#define LORA_RED_DOUBLES (4 * 2 * LORA_MAX_SF) /* 4 waves x 24 maxima */
+
+/* ln I0(x), x >= 0, for the SOFT log-likelihoods. Below 20 the power series
+ * sum_j (x^2/4)^j / (j!)^2 the reference sums (fft_demod.rs:9-23), all
+ * terms positive, cut where a term falls under 1e-17 of the sum (at most
+ * ~50 terms); from 20 on Hankel's expansion I0(x) = e^x / sqrt(2 pi x) *
+ * sum_k ((2k-1)!!)^2 / (k! (8x)^k), whose smallest term is ~e^(-2x) <=
+ * 4e-18 there, so ln I0 = x - ln(2 pi x)/2 + ln(sum) never forms e^709.
+ * Both agree with the reference's series to a few ulp of the sum. */
+#define LORA_I0_TERMS 96
+struct LoraInvSquares { /* v[j] = 1/j^2: the series without a division */
+    double v[LORA_I0_TERMS];
+    constexpr LoraInvSquares() : v() {
+        for (int j = 1; j < LORA_I0_TERMS; j++)
+            v[j] = 1.0 / ((double)j * (double)j);
+    }
+};
+static constexpr LoraInvSquares lora_inv_sq;
+
+__host__ __device__ static inline double lora_log_i0(double x) {
+    x = fabs(x);
+    if (x < 20.0) {
+        const double base = 0.25 * x * x;
+        double add = 1.0, sum = 1.0;
+        for (int j = 1; j < LORA_I0_TERMS; j++) {
+            add *= base * lora_inv_sq.v[j];
+            sum += add;
+            if (add < 1e-17 * sum) break;
+        }
+        return log(sum);
+    }
+    const double r = 0.125 / x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 64; k++) {
+        const double m = (double)(2 * k - 1);
+        const double next = term * (m * m * r / (double)k);
+        if (!(next < term)) break; /* the expansion has turned */
+        term = next;
+        sum += term;
+        if (term < 1e-17 * sum) break;
+    }
+    return x - 0.5 * log(6.283185307179586476925 * x) + log(sum);
+}
+
+/* Reduce v over the tps threads of a symbol (tps a power of two, the
+ * symbol's threads contiguous and aligned to it): xor butterflies inside a
+ * wave, then one exchange through sc (4 entries, one per wave) when the
+ * symbol spans several waves. Every thread of the symbol gets the result.
+ * op must be commutative and associative. Called by the whole block. */
+template <class T, class Op>
+__device__ __forceinline__ T lora_sym_reduce(T v, Op op, int tps, T* sc) {
+    const int w = tps < 64 ? tps : 64;
+    for (int off = w >> 1; off; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
+    if (tps > 64) {
+        const int wv = threadIdx.x >> 6, nw = tps >> 6;
+        const int w0 = (threadIdx.x / tps) * nw;
+        if ((threadIdx.x & 63) == 0) sc[wv] = v;
+        __syncthreads();
+        v = sc[w0];
+        for (int k = 1; k < nw; k++) v = op(v, sc[w0 + k]);
+        __syncthreads();
+    }
+    return v;
+}
+
+/* E = N * spb / 256 samples per thread, so a symbol's staging loads are
+ * issued together. n_sym whole symbols; out is u16[n_sym] (RAW, HARD) or
+ * f64[n_sym][12] (SOFT). Dynamic LDS: 2 * spb * N float2, then
+ * LORA_RED_DOUBLES doubles. */
+template <int MODE, int E>
+__global__ __launch_bounds__(LORA_BLOCK) void k_lora_demod(
+    const float2* __restrict__ in, void* __restrict__ out,
+    const float2* __restrict__ chirp, const float2* __restrict__ twid,
+    int sf, int spb, int reduced, long long n_sym) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int n = 1 << sf;
+    float2* ping = (float2*)smem;
+    float2* pong = ping + (size_t)spb * n;
+    double* red = (double*)(pong + (size_t)spb * n);
+    const int tps = LORA_BLOCK / spb;      /* threads per symbol */
+    const int sl = threadIdx.x / tps;      /* symbol within the block */
+    const int ts = threadIdx.x - sl * tps; /* thread within the symbol */
+    const int div = reduced ? 4 : 1;
+    const long long n_batches = (n_sym + spb - 1) / spb;
+    for (long long bt = blockIdx.x; bt < n_batches; bt += gridDim.x) {
+        const long long sym = bt * spb + sl;
+        const bool live = sym < n_sym;
+        float2* a = ping + (size_t)sl * n;
+        float2* b = pong + (size_t)sl * n;
+        {
+            /* volk_32fc_x2_multiply_32fc(samples, downchirp); a symbol
+             * past the end stages zeros and stores nothing */
+            float2 x[E], c[E];
+            const float2* src = in + (live ? sym : 0) * n;
+#pragma unroll
+            for (int u = 0; u < E; u++) {
+                x[u] = live ? src[ts + u * tps] : make_float2(0.f, 0.f);
+                c[u] = chirp[ts + u * tps];
+            }
+#pragma unroll
+            for (int u = 0; u < E; u++)
+                a[fft_swz((unsigned)(ts + u * tps))] = cmulf(x[u], c[u]);
+        }
+        __syncthreads();
+        const float2* res = fft_pow2_fwd(a, b, twid, n, ts, tps);
+        float* mag = (float*)(res == a ? b : a); /* the idle buffer */
+        /* |X|^2 as volk_32fc_magnitude_squared_32f (no contraction), and
+         * the argmax under max_by(total_cmp): the magnitudes are >= +0, so
+         * their bit patterns order as unsigned and (bits << 32 | index)
+         * has the largest magnitude, then the last index, as its maximum */
+        unsigned long long key = 0;
+#pragma unroll
+        for (int u = 0; u < E; u++) {
+            const int i = ts + u * tps;
+            const float2 v = res[fft_swz((unsigned)i)];
+            const float m =
+                __fadd_rn(__fmul_rn(v.x, v.x), __fmul_rn(v.y, v.y));
+            const unsigned long long k =
+                ((unsigned long long)__float_as_uint(m) << 32) | (unsigned)i;
+            key = k > key ? k : key;
+            if (MODE == LORA_SOFT) mag[i] = m; /* read back by this thread */
+        }
+        key = lora_sym_reduce(
+            key,
+            [](unsigned long long p, unsigned long long q) {
+                return p > q ? p : q;
+            },
+            tps, (unsigned long long*)red);
+        const int idx = (int)(unsigned)key;
+        const float top = __uint_as_float((unsigned)(key >> 32));
+        if (MODE == LORA_RAW) {
+            /* utils.rs:1071-1077: None where the f64 sum of the bins is 0,
+             * which for magnitudes >= 0 is where the largest is 0 */
+            if (live && ts == 0)
+                ((unsigned short*)out)[sym] =
+                    top == 0.f ? (unsigned short)0xFFFF : (unsigned short)idx;
+        } else if (MODE == LORA_HARD) {
+            if (live && ts == 0)
+                ((unsigned short*)out)[sym] =
+                    (unsigned short)(((idx - 1) & (n - 1)) / div);
+        } else {
+            auto add = [](double p, double q) { return p + q; };
+            double sig = 0.0, noi = 0.0;
+#pragma unroll
+            for (int u = 0; u < E; u++) {
+                const int i = ts + u * tps;
+                const int d = i > idx ? i - idx : idx - i;
+                const double m = (double)mag[i];
+                if (d % (n - 1) < 2) sig += m; else noi += m;
+            }
+            sig = lora_sym_reduce(sig, add, tps, red);
+            noi = lora_sym_reduce(noi, add, tps, red);
+            const double ps = sig / (double)n, pn = noi / (double)(n - 3);
+            const double K = sqrt(ps) / pn;
+            /* the argument grows with the magnitude, so "any bin reaches
+             * 709" is "the largest bin does" */
+            const bool clip = !(K * sqrt((double)top * (double)n) < 709.0);
+            /* ll_n grows with the magnitude in either branch, so the
+             * maximum of ll over a set of bins is ll of the set's largest
+             * magnitude: the 2 * sf maxima are taken over the f32
+             * magnitudes and ln I0 runs 2 * sf times per symbol, not N.
+             * -1 marks a set without bins (its maximum stays 0). */
+            float mx1[LORA_MAX_SF], mx0[LORA_MAX_SF];
+#pragma unroll
+            for (int bit = 0; bit < LORA_MAX_SF; bit++)
+                mx1[bit] = mx0[bit] = -1.f;
+#pragma unroll
+            for (int u = 0; u < E; u++) {
+                const int i = ts + u * tps;
+                const float m = mag[i];
+                int s = ((i - 1) & (n - 1)) / div;
+                s ^= s >> 1; /* Gray map, fft_demod.rs:192-194 */
+#pragma unroll
+                for (int bit = 0; bit < LORA_MAX_SF; bit++) {
+                    const bool one = (s >> bit) & 1;
+                    mx1[bit] = fmaxf(mx1[bit], one ? m : -1.f);
+                    mx0[bit] = fmaxf(mx0[bit], one ? -1.f : m);
+                }
+            }
+            /* the 24 maxima: butterflies, then one exchange for all */
+            const int w = tps < 64 ? tps : 64;
+#pragma unroll
+            for (int bit = 0; bit < LORA_MAX_SF; bit++) {
+                for (int off = w >> 1; off; off >>= 1) {
+                    mx1[bit] = fmaxf(mx1[bit], __shfl_xor(mx1[bit], off, 64));
+                    mx0[bit] = fmaxf(mx0[bit], __shfl_xor(mx0[bit], off, 64));
+                }
+            }
+            if (tps > 64) {
+                float* redf = (float*)red;
+                const int wv = threadIdx.x >> 6, nw = tps >> 6;
+                const int w0 = sl * nw;
+                if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+                    for (int bit = 0; bit < LORA_MAX_SF; bit++) {
+                        redf[wv * 2 * LORA_MAX_SF + 2 * bit] = mx1[bit];
+                        redf[wv * 2 * LORA_MAX_SF + 2 * bit + 1] = mx0[bit];
+                    }
+                }
+                __syncthreads();
+                for (int k = 0; k < nw; k++) {
+                    const float* r = redf + (w0 + k) * 2 * LORA_MAX_SF;
+#pragma unroll
+                    for (int bit = 0; bit < LORA_MAX_SF; bit++) {
+                        mx1[bit] = fmaxf(mx1[bit], r[2 * bit]);
+                        mx0[bit] = fmaxf(mx0[bit], r[2 * bit + 1]);
+                    }
+                }
+            }
+            /* every lane now holds all 24; lane j < 24 of the symbol turns
+             * number j (max_x1 of bit j/2 for even j, max_x0 for odd) into
+             * its ll, and the even lane next to it writes the difference:
+             * llrs[sf-1-bit] = max_x1 - max_x0, MSB first; the rest 0 */
+            for (int base = 0; base < 2 * LORA_MAX_SF; base += tps) {
+                const int j = base + ts;
+                float m = -1.f;
+#pragma unroll
+                for (int bit = 0; bit < LORA_MAX_SF; bit++) {
+                    m = j == 2 * bit ? mx1[bit] : m;
+                    m = j == 2 * bit + 1 ? mx0[bit] : m;
+                }
+                double ll = 0.0;
+                if (m >= 0.f) {
+                    const double mn = (double)m * (double)n;
+                    ll = clip ? mn : lora_log_i0(K * sqrt(mn));
+                }
+                const double d = ll - __shfl_xor(ll, 1, 64);
+                const int bit = j >> 1;
+                if (live && !(j & 1) && bit < LORA_MAX_SF)
+                    ((double*)out)[sym * LORA_MAX_SF +
+                                   (bit < sf ? sf - 1 - bit : bit)] =
+                        bit < sf ? d : 0.0;
+            }
+        }
+        __syncthreads(); /* the buffers are restaged next */
+    }
+}
+
 /* ================= host-side status math ============================== */
 
 static size_t sat_sub(size_t a, size_t b) { return a > b ? a - b : 0; }
@@ -3854,7 +4109,7 @@ static fsdr_filter_result resamp_status(size_t L, size_t M, size_t nt_total,
 enum FilterKind { K_FIR_CF32, K_FIR_F32, K_DECIM_CF32, K_RESAMP_CF32,
                   K_FFT_CF32, K_MAG2, K_FIR_CCF32, K_MOVAVG,
                   K_XLATING, K_PFB, K_PFB_SYNTH, K_PFB_ARB, K_RESAMP_F32,
-                  K_QUAD_DEMOD, K_FM_DEMOD_RESAMP, K_IIR_F32 };
+                  K_QUAD_DEMOD, K_FM_DEMOD_RESAMP, K_IIR_F32, K_LORA_DEMOD };
 
 struct fsdr_filter {
     FilterKind kind;
@@ -3926,6 +4181,11 @@ struct fsdr_filter {
      * memory.len(), the fill count. d_scratch: tile states, then the
      * states entering each tile. */
     fsdr_iir_plan* iir = nullptr;
+    /* LoRa FFT demodulator: n_taps = fft_len = N = 2^lora_sf, d_chirp the
+     * downchirp table of the current frame (N entries), d_twid the N-point
+     * twiddles; lora_mode one of LORA_RAW/HARD/SOFT. */
+    unsigned lora_sf = 0;
+    int lora_mode = 0, lora_reduced = 0;
 };
 
 static int ensure_dev(void** p, size_t* cur, size_t want) {
@@ -5004,6 +5264,123 @@ extern "C" const fsdr_iir_plan* fsdr_iir_plan_of(const fsdr_filter* f) {
     return f && f->kind == K_IIR_F32 ? f->iir : nullptr;
 }
 
+/* ---- LoRa FFT demodulator: tables, counts, handle --------------------- */
+
+/* conj(build_upchirp(0, sf, 1, preamble)) rotated by the frame's cfo and
+ * rounded to f32. The chirp is utils.rs:884-914 in f32 and in its
+ * operation order (the phase reaches ~1.3e4 rad at sf 12, so its f32
+ * rounding is part of the definition): id = my_modulo(0 - 1, N) = N - 1
+ * and n_fold = 1 for the demodulator's table (preamble false), id = 0 and
+ * n_fold = N for build_ref_chirps' (preamble true). Conjugate
+ * (fft_demod.rs:280-283) and rotation e^{-2 pi i (cfo_int + cfo_frac)/N * j}
+ * (:384-398) are in f64. */
+static void lora_downchirp_table(unsigned sf, bool preamble,
+                                 long long cfo_int, double cfo_frac,
+                                 fsdr_cf32* out) {
+#pragma clang fp contract(off)
+    const size_t n = (size_t)1 << sf;
+    const size_t id = preamble ? 0 : n - 1;
+    const size_t n_fold = n - id;
+    const float nf = (float)n;
+    const float pi = 3.14159265358979323846f;
+    for (size_t j = 0; j < n; j++) {
+        const float t = (float)j / 1.0f;
+        const float off = j < n_fold ? 0.5f : 1.5f;
+        const float ph =
+            2.0f * pi * (t * t / (2.f * nf) + ((float)id / nf - off) * t);
+        const double xr = (double)cosf(ph), xi = -(double)sinf(ph);
+        const double th = -2.0 * M_PI * ((double)cfo_int + cfo_frac) /
+                          (double)n * (double)j;
+        const double pr = cos(th), pi_ = sin(th);
+        out[j].re = (float)(xr * pr - xi * pi_);
+        out[j].im = (float)(xr * pi_ + xi * pr);
+    }
+}
+
+static bool lora_sf_ok(unsigned sf) { return sf >= 5 && sf <= LORA_MAX_SF; }
+
+extern "C" int fsdr_lora_downchirp(unsigned sf, long long cfo_int,
+                                   double cfo_frac, fsdr_cf32* out) {
+    if (!lora_sf_ok(sf) || !out) {
+        set_err("lora: sf must be in [5,12]");
+        return FSDR_ERR_INVALID;
+    }
+    lora_downchirp_table(sf, false, cfo_int, cfo_frac, out);
+    return FSDR_OK;
+}
+
+extern "C" double fsdr_lora_log_i0(double x) { return lora_log_i0(x); }
+
+extern "C" int fsdr_lora_demod_count(unsigned sf, size_t n_in, size_t n_out,
+                                     size_t* consumed, size_t* produced,
+                                     int* status) {
+    if (!lora_sf_ok(sf)) {
+        set_err("lora: sf must be in [5,12]");
+        return FSDR_ERR_INVALID;
+    }
+    const fsdr_filter_result r =
+        decim_status((size_t)1 << sf, n_in, 1, n_out);
+    if (consumed) *consumed = r.consumed;
+    if (produced) *produced = r.produced;
+    if (status) *status = (int)r.status;
+    return FSDR_OK;
+}
+
+static int lora_upload_chirp(fsdr_filter* f, long long cfo_int,
+                             double cfo_frac) {
+    std::vector<fsdr_cf32> t(f->fft_len);
+    lora_downchirp_table(f->lora_sf, f->lora_mode == LORA_RAW, cfo_int,
+                         cfo_frac, t.data());
+    HIP_TRY(hipMemcpy(f->d_chirp, t.data(), t.size() * sizeof(fsdr_cf32),
+                      hipMemcpyHostToDevice));
+    return FSDR_OK;
+}
+
+extern "C" fsdr_filter* fsdr_lora_demod_create(unsigned sf, int mode) {
+    if (!lora_sf_ok(sf)) {
+        set_err("lora: sf must be in [5,12]");
+        return nullptr;
+    }
+    if (mode != LORA_RAW && mode != LORA_HARD && mode != LORA_SOFT) {
+        set_err("lora: mode must be FSDR_LORA_RAW, _HARD or _SOFT");
+        return nullptr;
+    }
+    fsdr_filter* f = create_common(K_LORA_DEMOD);
+    if (!f) return nullptr;
+    const size_t n = (size_t)1 << sf;
+    f->lora_sf = sf;
+    f->lora_mode = mode;
+    f->fft_len = n;
+    f->n_taps = n; /* length() = set_min_items(N), fft_demod.rs:269 */
+    f->item_out = mode == LORA_SOFT ? LORA_MAX_SF * sizeof(double) : 2;
+    std::vector<float2> tw(n);
+    for (size_t k = 0; k < n; k++) {
+        const double a = -2.0 * M_PI * (double)k / (double)n;
+        tw[k] = make_float2((float)cos(a), (float)sin(a));
+    }
+    if (hipMalloc(&f->d_twid, n * sizeof(float2)) != hipSuccess ||
+        hipMemcpy(f->d_twid, tw.data(), n * sizeof(float2),
+                  hipMemcpyHostToDevice) != hipSuccess ||
+        hipMalloc(&f->d_chirp, n * sizeof(float2)) != hipSuccess ||
+        lora_upload_chirp(f, 0, 0.0) != FSDR_OK) {
+        set_err("lora table upload failed");
+        fsdr_filter_destroy(f);
+        return nullptr;
+    }
+    return f;
+}
+
+extern "C" int fsdr_lora_demod_set_frame(fsdr_filter* f, long long cfo_int,
+                                         double cfo_frac, int reduced_rate) {
+    REQUIRE_GPU();
+    if (!f || f->kind != K_LORA_DEMOD) {
+        set_err("not a lora demodulator");
+        return FSDR_ERR_INVALID;
+    }
+    f->lora_reduced = reduced_rate != 0;
+    return lora_upload_chirp(f, cfo_int, cfo_frac);
+}
+
 extern "C" fsdr_filter* fsdr_moving_avg_create(size_t width,
                                                float decay_factor,
                                                size_t history) {
@@ -5448,6 +5825,55 @@ static int launch_resamp_f32(const fsdr_filter* f, const float* d_in,
     return FSDR_OK;
 }
 
+/* Symbols per block of the LoRa kernel, like the Stockham kernel's frames
+ * per block: 1024 samples' worth, at most 16, at least one. */
+static int lora_spb(unsigned sf) {
+    const int n = 1 << sf;
+    return n >= 1024 ? 1 : std::min(16, 1024 / n);
+}
+
+static int launch_lora(const fsdr_filter* f, const void* d_in, void* d_out,
+                       size_t n_sym, hipStream_t st) {
+    if (n_sym == 0) return FSDR_OK;
+    const int n = 1 << f->lora_sf, spb = lora_spb(f->lora_sf);
+    const size_t lds = 2 * (size_t)spb * n * sizeof(float2) +
+                       LORA_RED_DOUBLES * sizeof(double);
+    const long long batches = ((long long)n_sym + spb - 1) / spb;
+    const int grid = (int)std::min<long long>(batches, grid_cap(256 * 8));
+    /* sf 12 needs 64 KiB + the reduction scratch: opt in past 64 KiB */
+#define LORA_LAUNCH(MODE_, E_)                                               \
+    do {                                                                     \
+        static bool lds_opt_in = false;                                      \
+        if (!lds_opt_in) {                                                   \
+            HIP_TRY(hipFuncSetAttribute(                                     \
+                (const void*)k_lora_demod<MODE_, E_>,                        \
+                hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));    \
+            lds_opt_in = true;                                               \
+        }                                                                    \
+        hipLaunchKernelGGL((k_lora_demod<MODE_, E_>), dim3(grid),            \
+                           dim3(LORA_BLOCK), lds, st, (const float2*)d_in,   \
+                           d_out, (const float2*)f->d_chirp,                 \
+                           (const float2*)f->d_twid, (int)f->lora_sf, spb,   \
+                           f->lora_reduced, (long long)n_sym);               \
+    } while (0)
+#define LORA_LAUNCH_E(MODE_)                                                 \
+    switch (n * spb / LORA_BLOCK) {                                          \
+        case 2: LORA_LAUNCH(MODE_, 2); break;                                \
+        case 4: LORA_LAUNCH(MODE_, 4); break;                                \
+        case 8: LORA_LAUNCH(MODE_, 8); break;                                \
+        default: LORA_LAUNCH(MODE_, 16); break;                              \
+    }
+    switch (f->lora_mode) {
+        case LORA_RAW: LORA_LAUNCH_E(LORA_RAW); break;
+        case LORA_HARD: LORA_LAUNCH_E(LORA_HARD); break;
+        default: LORA_LAUNCH_E(LORA_SOFT); break;
+    }
+#undef LORA_LAUNCH_E
+#undef LORA_LAUNCH
+    HIP_TRY(hipGetLastError());
+    return FSDR_OK;
+}
+
 /* `last` <- d_in[consumed-1], ordered after the kernel that read it */
 /* n > 0 outputs of the IIR from the live memory half; the new memory goes
  * to the other half. Up to three launches (no feedback: one; one tile:
@@ -5836,6 +6262,11 @@ extern "C" int fsdr_filter_dev(fsdr_filter* f, const void* d_in, size_t n_in,
             if (r->produced == 0) return FSDR_OK;
             return launch_iir(f, (const float*)d_in, (float*)d_out,
                               (long long)r->produced, st);
+        }
+        case K_LORA_DEMOD: {
+            /* whole symbols only: a trailing partial one stays unconsumed */
+            *r = decim_status(f->n_taps, n_in, 1, n_out);
+            return launch_lora(f, d_in, d_out, r->produced, st);
         }
         case K_MAG2: {
             size_t m = n_in < n_out ? n_in : n_out; /* apply.rs:108 */

@@ -195,6 +195,60 @@ void fsdr_iir_count(size_t n_a, size_t n_b, size_t filled, size_t n_in,
 fsdr_filter* fsdr_iir_f32_create(const float* a, size_t n_a, const float* b,
                                  size_t n_b);
 const fsdr_iir_plan* fsdr_iir_plan_of(const fsdr_filter* f);
+/* LoRa FFT demodulator — the arithmetic of examples/lora FftDemod
+ * (src/fft_demod.rs) and of FrameSync's get_symbol_val (src/utils.rs:
+ * 1059-1078) in one kernel: a symbol of N = 2^sf Complex32 samples times
+ * the handle's downchirp table, N-point forward unnormalized FFT, |X|^2 =
+ * re*re + im*im in f32, and a reduction over the bins fixed per handle:
+ *  FSDR_LORA_RAW   u16 out: argmax under max_by(total_cmp), the LAST of
+ *    equal maxima (utils.rs:1101-1109), or 0xFFFF (the reference's None)
+ *    where the f64 sum of the bins is exactly 0.
+ *  FSDR_LORA_HARD  u16 out: ((argmax - 1) mod N) / (reduced_rate ? 4 : 1)
+ *    (fft_demod.rs:115-120, 238-248); no zero-energy case.
+ *  FSDR_LORA_SOFT  double[12] out: compute_llrs' max-log branch
+ *    (fft_demod.rs:126-208; max_log_approx is hard-wired true at :278) in
+ *    f64 on the f32 magnitudes: bins with (|i - argmax| mod (N-1)) < 2 are
+ *    signal, ps = signal/N, pn = noise/(N-3), a_n = sqrt(ps)/pn *
+ *    sqrt(N*mag_n), ll_n = ln I0(a_n), or N*mag_n for every bin where any
+ *    a_n >= 709; for bit i < sf, with s = gray(((n-1) mod N) /
+ *    (reduced_rate ? 4 : 1)), out[sf-1-i] = max over bins with bit i of s
+ *    set minus max over the others, both maxima starting at 0; out[sf..11]
+ *    = 0. NaN/Inf input and all-zero input (pn = 0) are unspecified.
+ * _create: sf in [5,12] and one of the modes, else NULL plus an error
+ *   string. The handle is an fsdr_filter: fsdr_filter_host/_dev, _destroy
+ *   and fsdr_fg_add_filter take it; length() is N (set_min_items,
+ *   fft_demod.rs:269), items are 8 bytes in and 2 or 96 bytes out, and one
+ *   call returns produced = min(n_in / N, n_out), consumed = produced * N
+ *   with the decimating-FIR status rule for D = N and one tap. A trailing
+ *   partial symbol is never read and nothing is written past `produced`.
+ *   The kernel is stateless across symbols.
+ * _set_frame: the per-frame state the reference takes from the frame_info
+ *   tag (fft_demod.rs:355-399); the caller computes reduced_rate as :72-75
+ *   does. Rebuilds the table on the host in f64 and uploads it with a
+ *   blocking copy: call it between frames, not while a call that uses the
+ *   old table is in flight on a non-blocking stream. A fresh handle has
+ *   cfo 0 and reduced_rate 0. RAW ignores reduced_rate; its table is the
+ *   downchirp of build_ref_chirps (utils.rs:1053-1057) under the same
+ *   rotation. Tag parsing, the 4+cr symbol blocking and the frame-sync
+ *   state machine stay with the caller.
+ * fsdr_lora_downchirp (host-only): the HARD/SOFT table, N entries —
+ *   build_upchirp(0, sf, 1, false) (utils.rs:884-914) in f32 arithmetic in
+ *   the reference's operation order, conjugated in f64 (the constructor
+ *   path fft_demod.rs:280-283; set_sf at :54-57 omits the conjugate and is
+ *   out of scope, the handle's sf being fixed), rotated by
+ *   e^{-2 pi i (cfo_int + cfo_frac)/N * j} in f64, rounded to f32.
+ * fsdr_lora_log_i0 (host-only): the ln I0 evaluator the SOFT kernel runs.
+ * fsdr_lora_demod_count (host-only): the counts of one call alone.
+ * _downchirp and _count return FSDR_ERR_INVALID for sf outside [5,12]. */
+enum { FSDR_LORA_RAW = 0, FSDR_LORA_HARD = 1, FSDR_LORA_SOFT = 2 };
+fsdr_filter* fsdr_lora_demod_create(unsigned sf, int mode);
+int fsdr_lora_demod_set_frame(fsdr_filter* f, long long cfo_int,
+                              double cfo_frac, int reduced_rate);
+int fsdr_lora_downchirp(unsigned sf, long long cfo_int, double cfo_frac,
+                        fsdr_cf32* out);
+double fsdr_lora_log_i0(double x);
+int fsdr_lora_demod_count(unsigned sf, size_t n_in, size_t n_out,
+                          size_t* consumed, size_t* produced, int* status);
 /* Fft block — pow2 lengths in [4,4096] run the radix-4 Stockham kernel;
  * ANY other length in [2,2048] runs via Bluestein (two pow2 M>=2len-1
  * passes; the reference block is generic over rustfft plan lengths,

@@ -5,7 +5,7 @@ shapes, the standalone FFT kernel, and the PFB synthesizer (fused and
 staged path per shape, plus the channelizer at the same shape for
 context). Prints TF/s or GB/s vs peak. --synth runs the PFB synthesizer
 part only, --arb the PFB arbitrary-rate resampler part only, --iir the IIR
-filter part only."""
+filter part only, --lora the LoRa FFT demodulator part only."""
 import ctypes
 import os
 import sys
@@ -190,6 +190,79 @@ def iir_lines(lib, st, d_in, d_out, S, rounds=5):
         print(line)
 
 
+def lora_symbols(sf, S, snr_lin, seed):
+    """S device-resident samples of random LoRa symbols (the chirp of a
+    random id per symbol, phase formed in float64) plus complex Gaussian
+    noise of variance 1/snr_lin."""
+    n = 1 << sf
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    ids = torch.randint(0, n, (S // n, 1), generator=g,
+                        device="cuda").to(torch.float64)
+    t = torch.arange(n, device="cuda", dtype=torch.float64)[None, :]
+    ph = (t * t / (2.0 * n) + (ids / n - 0.5) * t) % 1.0
+    ph = (ph * (2.0 * np.pi)).to(torch.float32).reshape(-1)
+    del ids, t
+    x = torch.polar(torch.ones_like(ph), ph)
+    del ph
+    sd = float(np.sqrt(0.5 / snr_lin))
+    x += sd * torch.view_as_complex(
+        torch.randn(S, 2, generator=g, device="cuda", dtype=torch.float32))
+    return x
+
+
+def lora_lines(lib, st, d_out, S, rounds=5):
+    """LoRa FFT demodulator over S device-resident samples of whole symbols
+    in one call, sf 7, 9 and 12: the fused HARD call, the fused SOFT call
+    in its ln I0 branch (largest Bessel argument near 300) and in its
+    clipped branch (near 3000), against what the library composes the same
+    arithmetic from today, of which only the Stockham FFT with its |X|^2
+    output is timed (the dechirp product before it and the reduction after
+    it would come on top), and a device-to-device copy of the same 8
+    B/sample. `rounds` timings of each (5 back-to-back calls after 2
+    warm-up calls), the legs interleaved; median and range, the rate at the
+    op's floor of 8 B/sample, and the ratio to the FFT + |X|^2 call."""
+    d_mag = ctypes.c_void_p()
+    assert lib.fsdr_dev_alloc(ctypes.byref(d_mag), S * 4) == 0
+    dst = torch.empty(S, dtype=torch.complex64, device="cuda")
+    for sf in (7, 9, 12):
+        n = 1 << sf
+        k = S // n
+        lo = lora_symbols(sf, S, 300.0 / n, seed=sf)
+        hi = lora_symbols(sf, S, 3000.0 / n, seed=100 + sf)
+        hard = fa.LoraFftDemod(sf, fa.LORA_HARD)
+        soft = fa.LoraFftDemod(sf, fa.LORA_SOFT)
+        fft = fa.Fft(n)
+        s = st.cuda_stream
+        legs = [
+            ("HARD", lambda: hard.filter_dev(lo.data_ptr(), S, d_out.value,
+                                             k, stream=s)),
+            ("SOFT ln I0", lambda: soft.filter_dev(lo.data_ptr(), S,
+                                                   d_out.value, k, stream=s)),
+            ("SOFT clipped", lambda: soft.filter_dev(hi.data_ptr(), S,
+                                                     d_out.value, k,
+                                                     stream=s)),
+            ("fft + |X|^2", lambda: fft.bulk_dev(lo.data_ptr(), d_out.value,
+                                                 k, d_mag=d_mag.value,
+                                                 stream=s)),
+            ("d2d copy", lambda: dst.copy_(lo)),
+        ]
+        ms = [[] for _ in legs]
+        for _ in range(rounds):
+            for i, leg in enumerate(legs):
+                ms[i].append(timeit(leg[1], reps=5, warm=2))
+        fft_med = sorted(ms[3])[rounds // 2]
+        for i, (name, _) in enumerate(legs):
+            v = sorted(ms[i])
+            med = v[len(v) // 2]
+            tbs = S * 8 / (med * 1e-3) / 1e12
+            print(f"sf {sf:2d} {name:13s}: {med:7.3f} ms median of {rounds} "
+                  f"[{v[0]:.3f}..{v[-1]:.3f}]  {tbs:5.2f} TB/s at 8 B/sample "
+                  f"({tbs / PEAK_HBM:.3f} of HBM peak), "
+                  f"{med / fft_med:.2f}x fft + |X|^2")
+        del lo, hi
+    lib.fsdr_dev_free(d_mag)
+
+
 def main():
     lib = fa.lib()
     fa.set_device(0)
@@ -201,7 +274,9 @@ def main():
     assert lib.fsdr_dev_alloc(ctypes.byref(d_out), S * 8) == 0
     fa.fill_uniform_dev(d_in.value, S, seed=5, stream=st.cuda_stream)
 
-    if {"--synth", "--arb", "--iir"} & set(sys.argv[1:]):
+    if {"--synth", "--arb", "--iir", "--lora"} & set(sys.argv[1:]):
+        if "--lora" in sys.argv[1:]:
+            lora_lines(lib, st, d_out, S)
         if "--iir" in sys.argv[1:]:
             iir_lines(lib, st, d_in, d_out, S)
         if "--synth" in sys.argv[1:]:
