@@ -36,6 +36,7 @@
 #include <cmath>
 
 #include "../../include/futuresdr_hip.h"
+#include "dev_buf.h" /* after hip_runtime.h: it names HIP, includes none */
 
 /* ================= error plumbing ==================================== */
 
@@ -1656,23 +1657,21 @@ extern "C" int fsdr_chain_ubench(int mode, double* tflops, void* stream) {
     const int KKD = G::KKD;
     const long long n_out = 1 << 24; /* decimated outputs (2^26 inputs) */
     const long long n_in = 4 * n_out + 1024;
-    float* d_taps = nullptr;
-    float2* d_in = nullptr;
-    float2* d_out = nullptr;
-    float2* d_tw = nullptr;
-    HIP_TRY(hipMalloc(&d_taps, 4 * KKD * sizeof(float)));
-    HIP_TRY(hipMemset(d_taps, 1, 4 * KKD * sizeof(float)));
-    HIP_TRY(hipMalloc(&d_in, n_in * sizeof(float2)));
-    HIP_TRY(hipMemset(d_in, 2, n_in * sizeof(float2)));
-    HIP_TRY(hipMalloc(&d_out, n_out * sizeof(float2)));
+    dev_buf b_taps, b_in, b_out, b_tw; /* freed on every return */
+    HIP_TRY(b_taps.ensure(4 * KKD * sizeof(float)));
+    HIP_TRY(hipMemset(b_taps.ptr, 1, b_taps.bytes));
+    HIP_TRY(b_in.ensure(n_in * sizeof(float2)));
+    HIP_TRY(hipMemset(b_in.ptr, 2, b_in.bytes));
+    HIP_TRY(b_out.ensure(n_out * sizeof(float2)));
     std::vector<float2> tw(1024);
     for (int k = 0; k < 1024; k++) {
         double a = -2.0 * M_PI * k / 1024.0;
         tw[k] = make_float2((float)cos(a), (float)sin(a));
     }
-    HIP_TRY(hipMalloc(&d_tw, 1024 * sizeof(float2)));
-    HIP_TRY(hipMemcpy(d_tw, tw.data(), 1024 * sizeof(float2),
-                      hipMemcpyHostToDevice));
+    HIP_TRY(b_tw.upload(tw.data(), tw.size()));
+    float* d_taps = b_taps.as<float>();
+    float2 *d_in = b_in.as<float2>(), *d_out = b_out.as<float2>(),
+           *d_tw = b_tw.as<float2>();
     hipStream_t st = (hipStream_t)stream;
     int grid = 8192;
     hipEvent_t e0, e1;
@@ -1700,10 +1699,6 @@ extern "C" int fsdr_chain_ubench(int mode, double* tflops, void* stream) {
     *tflops = fl / (ms * 1e-3) / 1e12;
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    (void)hipFree(d_taps);
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    (void)hipFree(d_tw);
     return FSDR_OK;
 }
 
@@ -1713,11 +1708,12 @@ extern "C" int fsdr_mfma_ubench(int grid, int iters, double* tflops,
     using G = ChainGeom<80>;
     const int KKD = G::KKD;
     const size_t lds = G::halves_bytes;
-    float* d_taps = nullptr;
-    float2* d_out = nullptr;
-    HIP_TRY(hipMalloc(&d_taps, 4 * KKD * sizeof(float)));
-    HIP_TRY(hipMemset(d_taps, 1, 4 * KKD * sizeof(float)));
-    HIP_TRY(hipMalloc(&d_out, (size_t)grid * MDFIR_BLOCK * sizeof(float2)));
+    dev_buf b_taps, b_out; /* freed on every return */
+    HIP_TRY(b_taps.ensure(4 * KKD * sizeof(float)));
+    HIP_TRY(hipMemset(b_taps.ptr, 1, b_taps.bytes));
+    HIP_TRY(b_out.ensure((size_t)grid * MDFIR_BLOCK * sizeof(float2)));
+    float* d_taps = b_taps.as<float>();
+    float2* d_out = b_out.as<float2>();
     hipStream_t st = (hipStream_t)stream;
     hipEvent_t e0, e1;
     HIP_TRY(hipEventCreate(&e0));
@@ -1737,8 +1733,6 @@ extern "C" int fsdr_mfma_ubench(int grid, int iters, double* tflops,
     *tflops = fl / (ms * 1e-3) / 1e12;
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    (void)hipFree(d_taps);
-    (void)hipFree(d_out);
     return FSDR_OK;
 }
 
@@ -4111,91 +4105,185 @@ enum FilterKind { K_FIR_CF32, K_FIR_F32, K_DECIM_CF32, K_RESAMP_CF32,
                   K_XLATING, K_PFB, K_PFB_SYNTH, K_PFB_ARB, K_RESAMP_F32,
                   K_QUAD_DEMOD, K_FM_DEMOD_RESAMP, K_IIR_F32, K_LORA_DEMOD };
 
-struct fsdr_filter {
-    FilterKind kind;
-    size_t width = 0;        /* MovingAvg */
-    size_t history = 0;
-    size_t i_state = 0;
-    float decay = 0.f;        /* MovingAvg decay factor */
-    float theta = 0.f;        /* XlatingFir rotator increment */
-    float rot_re = 1.f, rot_im = 0.f; /* xlating rotator phase state */
-    fsdr_filter* sub = nullptr;       /* channelizer's internal IFFT */
-    float* d_avg = nullptr;
-    size_t n_taps = 0;       /* true tap count (length()) */
-    size_t decim = 1, interp = 1;
-    size_t fft_len = 0;
-    int inverse = 0, fft_shift = 0;
-    float norm = 0.f;
-    /* Bluestein (non-pow2 fft_len): M = next pow2 >= 2*len-1; chirp
-     * w(k) = e^{sigma*pi*i*k^2/len}; B = DFT_M of the wrapped conj
-     * chirp. fft.rs is generic over rustfft plan lengths; this closes
-     * the pow2-only gap via two pow2 M-point passes per batch. */
-    size_t fft_m = 0;
-    float2* d_chirp = nullptr;
-    float2* d_B = nullptr;
-    int n_taps_padded = 0;   /* device taps length (leading zeros) */
-    float* d_taps = nullptr;
-    int tp_tpl = 0;          /* template tap count (reversed taps) or 0 */
-    float* d_rtaps = nullptr; /* reversed taps zero-filled to tp_tpl */
-    int kk_mfma = 0;         /* MFMA variant K (>= n_taps+15, %4==0) */
-    float* d_mtaps = nullptr; /* reversed taps zero-filled to kk_mfma */
-    int kk_mfma32 = 0;       /* 32x32 variant K (>= n_taps+31, even) */
-    float* d_mtaps32 = nullptr;
-    float2* d_twid = nullptr;
-    /* staging buffers for the host-span path */
-    void* d_in = nullptr;
-    void* d_out = nullptr;
-    size_t d_in_bytes = 0, d_out_bytes = 0;
-    size_t item_in = 8, item_out = 8;
-    /* dedicated kernel scratch (MovingAvg chunk partials, PFB work
-     * buffer). MUST be distinct from d_in: on the fsdr_filter_host path
-     * d_in holds the staged input while the partials kernel is still
-     * reading it. */
-    void* d_scratch = nullptr;
-    size_t d_scratch_bytes = 0;
-    /* PFB streaming state: the last N*tpf CONSUMED samples (the window
-     * contents) + total pushes (channelizer.rs round-robin state) */
-    void* d_hist = nullptr;
-    size_t d_hist_bytes = 0;
-    size_t pfb_pushes = 0;
-    /* PFB synthesizer: d_taps is the transposed partition partT[j*N+c];
-     * d_hist holds two (tpf-1)*N-frame halves of IFFT'd history, the
-     * live one picked by i_state (a launch reads one and writes the
-     * other); pfb_pushes counts consumed steps; d_early keeps the
-     * IFFT'd frames of steps 0..2tpf-2 for the start-up rows. */
-    void* d_early = nullptr;
-    size_t d_early_bytes = 0;
-    /* PFB arb resampler: width = channels, history = tpf, d_taps the
-     * reversed partition rpart[f][t] = part[f][tpf-1-t]; arb is the owned
-     * schedule and d_ck its checkpoints on the device. d_hist holds two
-     * channels*tpf window copies, the live one picked by i_state;
-     * pfb_pushes counts consumed inputs, the tpf fill pushes included. */
-    fsdr_pfb_arb_schedule* arb = nullptr;
-    void* d_ck = nullptr;
-    /* QuadDemod / FM demod+resampler: d_hist is the one carried Complex32
-     * `last` (main.rs:99-104), zero on a fresh handle. */
-    /* IIR: d_taps = b, n_taps = nb; iir is the owned plan (a and the
-     * tables) and d_ck the tables on the device (H, chunk powers, tile
-     * powers). d_hist holds two IIR_NA_MAX-float copies of `memory`
-     * (memory[j] = y[-1-j]), the live one picked by i_state; pfb_pushes is
-     * memory.len(), the fill count. d_scratch: tile states, then the
-     * states entering each tile. */
-    fsdr_iir_plan* iir = nullptr;
-    /* LoRa FFT demodulator: n_taps = fft_len = N = 2^lora_sf, d_chirp the
-     * downchirp table of the current frame (N entries), d_twid the N-point
-     * twiddles; lora_mode one of LORA_RAW/HARD/SOFT. */
-    unsigned lora_sf = 0;
-    int lora_mode = 0, lora_reduced = 0;
+/* "On unless the variable parses to 0", and "the variable's integer value,
+ * or dflt when unset". Both read the environment on every call: the tests
+ * flip these switches between calls inside one process. */
+static bool env_on(const char* name) {
+    const char* e = getenv(name);
+    return !e || atoi(e) != 0;
+}
+static int env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
+
+/* Two copies of a carried state in one buffer, `n` items of T each. A
+ * launch reads live() and writes next(); the caller flips once the launch
+ * is enqueued. */
+struct carried_state {
+    dev_buf buf;
+    size_t i = 0;
+    template <class T>
+    T* live(size_t n) const { return buf.as<T>() + i * n; }
+    template <class T>
+    T* next(size_t n) const { return buf.as<T>() + (i ^ 1) * n; }
+    void flip() { i ^= 1; }
 };
 
-static int ensure_dev(void** p, size_t* cur, size_t want) {
-    if (*cur >= want) return FSDR_OK;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cur = 0;
-    HIP_TRY(hipMalloc(p, want));
-    *cur = want;
-    return FSDR_OK;
+/* A handle owns all of its device memory as dev_buf members, and its
+ * inner handles and host-side plans through ~fsdr_filter: destroying the
+ * handle is the only place any of it is released, so a *_create that
+ * fails part-way deletes the handle and returns null. Each block family
+ * keeps its state in its own member struct; a handle uses its family's
+ * and leaves the others empty. */
+struct fsdr_filter {
+    FilterKind kind;
+    size_t item_in = 8, item_out = 8;
+    size_t length = 0; /* what fsdr_filter_length reports (min_items) */
+    /* staging buffers of the host-span path (fsdr_filter_host) */
+    dev_buf stage_in, stage_out;
+
+    /* Fir, FirCC, FirF32, DecimatingFir, XlatingFir and the polyphase
+     * resamplers (FM back end included): the taps as the generic kernel
+     * of the kind reads them, and for the cf32 FIR and the decimating FIR
+     * the template variants picked at create, each with its own taps
+     * layout (0 = that variant does not apply). */
+    struct {
+        size_t n_taps = 0;   /* true tap count */
+        size_t decim = 1, interp = 1;
+        int n_padded = 0;    /* device taps length (leading zeros) */
+        dev_buf taps;
+        int tp_tpl = 0;      /* template tap count */
+        dev_buf rtaps;       /* reversed taps zero-filled to tp_tpl; for
+                                decimation 4, four phase rows of them */
+        int kk_mfma = 0;     /* MFMA variant K (>= n_taps+15, %4==0) */
+        dev_buf mtaps;       /* reversed taps zero-filled to kk_mfma */
+        int kk_mfma32 = 0;   /* 32x32 variant K (>= n_taps+31, even) */
+        dev_buf mtaps32;
+        /* 1:4 cf32 resampler: the decimating FIR whose MFMA kernel it
+         * launches */
+        fsdr_filter* decim4 = nullptr;
+    } fir;
+
+    /* XlatingFir: fir.taps holds the band-pass taps (float2, reversed) */
+    struct {
+        float theta = 0.f;                /* rotator increment */
+        float rot_re = 1.f, rot_im = 0.f; /* rotator phase, carried */
+    } xlat;
+
+    /* Fft. Bluestein (non-pow2 len): m = next pow2 >= 2*len-1; chirp
+     * w(k) = e^{sigma*pi*i*k^2/len}; B = DFT_m of the wrapped conj chirp.
+     * fft.rs is generic over rustfft plan lengths; this closes the
+     * pow2-only gap via two pow2 m-point passes per batch, in `work`. */
+    struct {
+        size_t len = 0;
+        int inverse = 0, shift = 0;
+        float norm = 0.f;
+        dev_buf twid;        /* len (Bluestein: m) twiddles */
+        size_t m = 0;        /* 0 = plain pow2 Stockham */
+        dev_buf chirp, B, work;
+    } fft;
+
+    /* MovingAvg */
+    struct {
+        size_t width = 0, history = 0;
+        size_t i = 0;        /* frames since the last emission */
+        float decay = 0.f;
+        dev_buf avg;         /* the EMA state, width floats */
+        /* chunk partials of the fast path. Not a staging buffer: on the
+         * host path stage_in holds the input that the partials kernel is
+         * still reading. */
+        dev_buf partials;
+    } movavg;
+
+    /* What the three PFB blocks share: the channel count, taps per
+     * polyphase filter, and (channelizer, synthesizer) the inner IFFT. */
+    struct {
+        size_t channels = 0, tpf = 0;
+        fsdr_filter* ifft = nullptr;
+    } pfb;
+
+    /* PFB channelizer. Streaming state: the last channels*tpf consumed
+     * samples and the total pushes (channelizer.rs round-robin state). */
+    struct {
+        size_t decim = 1;    /* channels / oversample_rate */
+        dev_buf taps;        /* part[i][c] = taps[i + c*channels] */
+        size_t pushes = 0;
+        dev_buf hist;
+        dev_buf work;        /* [hist, chunk] of one stream call */
+        dev_buf dots, spectra; /* IFFT input and output, steps*channels */
+    } chan;
+
+    /* PFB synthesizer. The stream carries the last tpf-1 IFFT'd frames
+     * and the IFFT'd frames of steps 0..2tpf-2 for the start-up rows; the
+     * one-shot entry point keeps its start-up frames apart so it leaves a
+     * stream on the same handle alone. */
+    struct {
+        dev_buf taps;        /* partT[j*channels + c]: partition, transposed */
+        size_t steps = 0;    /* consumed by the stream so far */
+        carried_state hist;  /* (tpf-1)*channels float2 per copy */
+        dev_buf early, early_oneshot;
+        dev_buf gathered, frames; /* staged path: IFFT input, [hist, IFFT'd] */
+    } synth;
+
+    /* PFB arb resampler: the owned schedule and its checkpoints on the
+     * device; the stream carries each channel's window of tpf samples. */
+    struct {
+        fsdr_pfb_arb_schedule* sched = nullptr;
+        dev_buf taps;        /* rpart[f][t] = part[f][tpf-1-t] */
+        dev_buf ck;
+        size_t consumed = 0; /* inputs so far, the tpf fill pushes included */
+        carried_state window; /* channels*tpf float2 per copy */
+        dev_buf window_oneshot;
+    } arb;
+
+    /* QuadDemod / FM demod+resampler: the carried Complex32 `last`
+     * (main.rs:99-104), zero on a fresh handle. */
+    struct {
+        dev_buf last;
+        dev_buf staged;      /* unfused FM path: the demodulated span */
+    } demod;
+
+    /* IIR: the owned plan (a and the tables) with the tables on the
+     * device (H, chunk powers, tile powers). mem[j] = y[-1-j]. */
+    struct {
+        fsdr_iir_plan* plan = nullptr;
+        size_t n_b = 0;
+        dev_buf b, tables;
+        size_t filled = 0;   /* memory.len(): the fill count */
+        carried_state mem;   /* IIR_NA_MAX floats per copy */
+        dev_buf tile_states; /* tile states, then the states entering each */
+    } iir;
+
+    /* LoRa FFT demodulator: N = 2^sf. */
+    struct {
+        unsigned sf = 0;
+        int mode = 0, reduced = 0; /* LORA_RAW/HARD/SOFT; reduced rate */
+        dev_buf chirp;       /* downchirp of the current frame, N entries */
+        dev_buf twid;        /* N-point twiddles */
+    } lora;
+
+    ~fsdr_filter(); /* below, once the plan types are complete */
+};
+
+/* Allocate exactly n items and copy them up; on failure set `err` and
+ * leave the buffer empty. */
+template <class T>
+static bool upload(dev_buf& b, const T* host, size_t n, const char* err) {
+    if (b.upload(host, n) == hipSuccess) return true;
+    set_err(err);
+    return false;
+}
+template <class T>
+static bool upload(dev_buf& b, const std::vector<T>& v, const char* err) {
+    return upload(b, v.data(), v.size(), err);
+}
+
+/* n zeroed bytes */
+static bool alloc_zeroed(dev_buf& b, size_t n, const char* err) {
+    if (b.ensure(n) == hipSuccess && b.zero() == hipSuccess) return true;
+    set_err(err);
+    return false;
 }
 
 /* pad taps to tp ≡ 1 (mod m) with leading zeros (zero taps
@@ -4206,11 +4294,36 @@ static int upload_taps_padded(fsdr_filter* f, const float* taps, size_t nt,
     while (tp % mod != 1 % mod) tp++;
     std::vector<float> h(tp, 0.f);
     memcpy(h.data() + (tp - nt), taps, nt * sizeof(float));
-    HIP_TRY(hipMalloc(&f->d_taps, tp * sizeof(float)));
-    HIP_TRY(hipMemcpy(f->d_taps, h.data(), tp * sizeof(float),
-                      hipMemcpyHostToDevice));
-    f->n_taps_padded = (int)tp;
+    HIP_TRY(f->fir.taps.upload(h.data(), tp));
+    f->fir.n_padded = (int)tp;
     return FSDR_OK;
+}
+
+/* taps reversed and zero-filled to `len` (>= nt) */
+static bool upload_reversed(dev_buf& b, const float* taps, size_t nt,
+                            size_t len, const char* err) {
+    std::vector<float> rt(len, 0.f);
+    for (size_t i = 0; i < nt; i++) rt[i] = taps[nt - 1 - i];
+    return upload(b, rt, err);
+}
+
+/* decimation-4 phase split: row v of `stride` floats holds
+ * h[nt-1-(4u+v)] at u < n_u, zeros elsewhere */
+static bool upload_phase_split(dev_buf& b, const float* taps, size_t nt,
+                               int n_u, int stride, const char* err) {
+    std::vector<float> rows(4 * (size_t)stride, 0.f);
+    for (int v = 0; v < 4; v++)
+        for (int u = 0; u < n_u; u++) {
+            size_t t = 4 * (size_t)u + v;
+            if (t < nt) rows[v * stride + u] = taps[nt - 1 - t];
+        }
+    return upload(b, rows, err);
+}
+
+/* a *_create that fails after the handle exists; the error is set */
+static fsdr_filter* create_failed(fsdr_filter* f) {
+    delete f;
+    return nullptr;
 }
 
 static fsdr_filter* create_common(FilterKind k) {
@@ -4228,50 +4341,23 @@ extern "C" fsdr_filter* fsdr_fir_cf32_create(const float* taps,
     if (!taps || n_taps == 0) { set_err("null/empty taps"); return nullptr; }
     fsdr_filter* f = create_common(K_FIR_CF32);
     if (!f) return nullptr;
-    f->n_taps = n_taps;
-    if (upload_taps_padded(f, taps, n_taps, 8) != FSDR_OK) {
-        delete f;
-        return nullptr;
-    }
-    /* template variant: reversed taps zero-filled to the smallest
-     * instantiated TP >= n_taps */
-    f->tp_tpl = tpl_at_least(fir_tpl_tps{}, n_taps);
-    if (f->tp_tpl) {
-        std::vector<float> rt(f->tp_tpl, 0.f);
-        for (size_t i = 0; i < n_taps; i++) rt[i] = taps[n_taps - 1 - i];
-        if (hipMalloc(&f->d_rtaps, rt.size() * sizeof(float)) != hipSuccess ||
-            hipMemcpy(f->d_rtaps, rt.data(), rt.size() * sizeof(float),
-                      hipMemcpyHostToDevice) != hipSuccess) {
-            set_err("reversed taps upload failed");
-            delete f;
-            return nullptr;
-        }
-    }
-    f->kk_mfma32 = tpl_at_least(fir_mfma32_ks{}, n_taps + 31);
-    if (f->kk_mfma32) {
-        std::vector<float> rt(f->kk_mfma32, 0.f);
-        for (size_t i = 0; i < n_taps; i++) rt[i] = taps[n_taps - 1 - i];
-        if (hipMalloc(&f->d_mtaps32, rt.size() * sizeof(float)) !=
-                hipSuccess ||
-            hipMemcpy(f->d_mtaps32, rt.data(), rt.size() * sizeof(float),
-                      hipMemcpyHostToDevice) != hipSuccess) {
-            set_err("mfma32 taps upload failed");
-            delete f;
-            return nullptr;
-        }
-    }
-    f->kk_mfma = tpl_at_least(fir_mfma_ks{}, n_taps + 15);
-    if (f->kk_mfma) {
-        std::vector<float> rt(f->kk_mfma, 0.f);
-        for (size_t i = 0; i < n_taps; i++) rt[i] = taps[n_taps - 1 - i];
-        if (hipMalloc(&f->d_mtaps, rt.size() * sizeof(float)) != hipSuccess ||
-            hipMemcpy(f->d_mtaps, rt.data(), rt.size() * sizeof(float),
-                      hipMemcpyHostToDevice) != hipSuccess) {
-            set_err("mfma taps upload failed");
-            delete f;
-            return nullptr;
-        }
-    }
+    f->length = f->fir.n_taps = n_taps;
+    /* the template variants take reversed taps zero-filled to the
+     * smallest instantiated size that fits */
+    f->fir.tp_tpl = tpl_at_least(fir_tpl_tps{}, n_taps);
+    f->fir.kk_mfma32 = tpl_at_least(fir_mfma32_ks{}, n_taps + 31);
+    f->fir.kk_mfma = tpl_at_least(fir_mfma_ks{}, n_taps + 15);
+    if (upload_taps_padded(f, taps, n_taps, 8) != FSDR_OK ||
+        (f->fir.tp_tpl &&
+         !upload_reversed(f->fir.rtaps, taps, n_taps, f->fir.tp_tpl,
+                          "reversed taps upload failed")) ||
+        (f->fir.kk_mfma32 &&
+         !upload_reversed(f->fir.mtaps32, taps, n_taps, f->fir.kk_mfma32,
+                          "mfma32 taps upload failed")) ||
+        (f->fir.kk_mfma &&
+         !upload_reversed(f->fir.mtaps, taps, n_taps, f->fir.kk_mfma,
+                          "mfma taps upload failed")))
+        return create_failed(f);
     return f;
 }
 
@@ -4280,15 +4366,10 @@ extern "C" fsdr_filter* fsdr_fir_ccf32_create(const fsdr_cf32* taps,
     if (!taps || n_taps == 0) { set_err("null/empty taps"); return nullptr; }
     fsdr_filter* f = create_common(K_FIR_CCF32);
     if (!f) return nullptr;
-    f->n_taps = n_taps;
-    f->n_taps_padded = (int)n_taps;
-    if (hipMalloc(&f->d_taps, n_taps * sizeof(fsdr_cf32)) != hipSuccess ||
-        hipMemcpy(f->d_taps, taps, n_taps * sizeof(fsdr_cf32),
-                  hipMemcpyHostToDevice) != hipSuccess) {
-        set_err("taps upload failed");
-        delete f;
-        return nullptr;
-    }
+    f->length = f->fir.n_taps = n_taps;
+    f->fir.n_padded = (int)n_taps;
+    if (!upload(f->fir.taps, taps, n_taps, "taps upload failed"))
+        return create_failed(f);
     return f;
 }
 
@@ -4297,17 +4378,11 @@ extern "C" fsdr_filter* fsdr_fir_f32_create(const float* taps,
     if (!taps || n_taps == 0) { set_err("null/empty taps"); return nullptr; }
     fsdr_filter* f = create_common(K_FIR_F32);
     if (!f) return nullptr;
-    f->n_taps = n_taps;
+    f->length = f->fir.n_taps = n_taps;
+    f->fir.n_padded = (int)n_taps;
     f->item_in = f->item_out = 4;
-    std::vector<float> h(taps, taps + n_taps);
-    if (hipMalloc(&f->d_taps, n_taps * sizeof(float)) != hipSuccess ||
-        hipMemcpy(f->d_taps, h.data(), n_taps * sizeof(float),
-                  hipMemcpyHostToDevice) != hipSuccess) {
-        set_err("taps upload failed");
-        delete f;
-        return nullptr;
-    }
-    f->n_taps_padded = (int)n_taps;
+    if (!upload(f->fir.taps, taps, n_taps, "taps upload failed"))
+        return create_failed(f);
     return f;
 }
 
@@ -4320,94 +4395,34 @@ extern "C" fsdr_filter* fsdr_decim_fir_cf32_create(size_t decimation,
     }
     fsdr_filter* f = create_common(K_DECIM_CF32);
     if (!f) return nullptr;
-    f->n_taps = n_taps;
-    f->decim = decimation;
+    f->length = f->fir.n_taps = n_taps;
+    f->fir.decim = decimation;
     int mod = (decimation == 4) ? 16 : 1; /* fast path needs tp%16==1 */
-    if (upload_taps_padded(f, taps, n_taps, mod) != FSDR_OK) {
-        delete f;
-        return nullptr;
-    }
+    if (upload_taps_padded(f, taps, n_taps, mod) != FSDR_OK)
+        return create_failed(f);
     if (decimation == 4 && n_taps <= 512) {
-        /* MFMA variant: per-phase K = ceil(T/4)+15 rounded to 4 */
+        /* MFMA variant: per-phase K = ceil(T/4)+15 rounded to 4; rows of
+         * K. Phase-split template: rows of tpd+4 holding tpd taps. */
         size_t tpd_true = (n_taps + 3) / 4;
-        f->kk_mfma = tpl_at_least(decim4_mfma_ks{}, tpd_true + 15);
-        if (f->kk_mfma) {
-            int kkd = f->kk_mfma;
-            std::vector<float> rm(4 * (size_t)kkd, 0.f);
-            for (int v = 0; v < 4; v++)
-                for (int u = 0; u < kkd; u++) {
-                    size_t t = 4 * (size_t)u + v;
-                    if (t < n_taps)
-                        rm[v * kkd + u] = taps[n_taps - 1 - t];
-                }
-            if (hipMalloc(&f->d_mtaps, rm.size() * sizeof(float)) !=
-                    hipSuccess ||
-                hipMemcpy(f->d_mtaps, rm.data(),
-                          rm.size() * sizeof(float),
-                          hipMemcpyHostToDevice) != hipSuccess) {
-                set_err("decim mfma taps upload failed");
-                delete f;
-                return nullptr;
-            }
-        }
-        /* phase-split template: rtv[v][u] = h[n_taps-1-(4u+v)] */
-        f->tp_tpl = tpl_at_least(decim4_tpl_tpds{}, tpd_true);
-        int tpd = f->tp_tpl;
-        std::vector<float> rtv(4 * (tpd + 4), 0.f);
-        for (int v = 0; v < 4; v++)
-            for (int u = 0; u < tpd; u++) {
-                size_t t = 4 * (size_t)u + v;
-                if (t < n_taps)
-                    rtv[v * (tpd + 4) + u] = taps[n_taps - 1 - t];
-            }
-        if (hipMalloc(&f->d_rtaps, rtv.size() * sizeof(float)) !=
-                hipSuccess ||
-            hipMemcpy(f->d_rtaps, rtv.data(), rtv.size() * sizeof(float),
-                      hipMemcpyHostToDevice) != hipSuccess) {
-            set_err("rtv upload failed");
-            delete f;
-            return nullptr;
-        }
+        const int kkd = f->fir.kk_mfma =
+            tpl_at_least(decim4_mfma_ks{}, tpd_true + 15);
+        const int tpd = f->fir.tp_tpl =
+            tpl_at_least(decim4_tpl_tpds{}, tpd_true);
+        if ((kkd && !upload_phase_split(f->fir.mtaps, taps, n_taps, kkd, kkd,
+                                        "decim mfma taps upload failed")) ||
+            !upload_phase_split(f->fir.rtaps, taps, n_taps, tpd, tpd + 4,
+                                "rtv upload failed"))
+            return create_failed(f);
     }
     return f;
 }
 
-extern "C" fsdr_filter* fsdr_resamp_cf32_create(size_t interp, size_t decim,
-                                                const float* taps,
-                                                size_t n_taps) {
-    if (!taps || n_taps == 0 || interp == 0 || decim == 0 ||
-        n_taps % interp != 0) {
-        /* polyphase_resampling_fir.rs:54-56 assert */
-        set_err("invalid resampler parameters (n_taps % interp must be 0)");
-        return nullptr;
-    }
-    fsdr_filter* f = create_common(K_RESAMP_CF32);
-    if (!f) return nullptr;
-    f->n_taps = n_taps;
-    f->interp = interp;
-    f->decim = decim;
-    if (hipMalloc(&f->d_taps, n_taps * sizeof(float)) != hipSuccess ||
-        hipMemcpy(f->d_taps, taps, n_taps * sizeof(float),
-                  hipMemcpyHostToDevice) != hipSuccess) {
-        set_err("taps upload failed");
-        delete f;
-        return nullptr;
-    }
-    f->n_taps_padded = (int)n_taps;
-    /* interp==1, decim==4 (the config-3 "4:1" shape): y[k] =
-     * sum_t x[4k+t]*h[T-1-t] is the decimating FIR evaluated with its
-     * window origin shifted by D-1, so route it to the MFMA decim
-     * kernel with the input pointer rebased (launch site). */
-    if (interp == 1 && decim == 4 && n_taps <= 512)
-        f->sub = fsdr_decim_fir_cf32_create(4, taps, n_taps);
-    return f;
-}
-
-/* The f32-items polyphase handles: argument check (decided before a GPU
- * is needed), then the taps upload. */
-static fsdr_filter* resamp_f32_like_create(FilterKind kind, size_t interp,
-                                           size_t decim, const float* taps,
-                                           size_t n_taps) {
+/* The polyphase handles: argument check (decided before a GPU is needed),
+ * then the taps upload. */
+static fsdr_filter* resamp_create(FilterKind kind, size_t item_in,
+                                  size_t item_out, size_t interp,
+                                  size_t decim, const float* taps,
+                                  size_t n_taps) {
     if (!taps || n_taps == 0 || interp == 0 || decim == 0 ||
         n_taps % interp != 0) {
         /* polyphase_resampling_fir.rs:54-56 assert */
@@ -4416,49 +4431,45 @@ static fsdr_filter* resamp_f32_like_create(FilterKind kind, size_t interp,
     }
     fsdr_filter* f = create_common(kind);
     if (!f) return nullptr;
-    f->n_taps = n_taps;
-    f->interp = interp;
-    f->decim = decim;
-    f->item_out = 4;
-    if (hipMalloc(&f->d_taps, n_taps * sizeof(float)) != hipSuccess ||
-        hipMemcpy(f->d_taps, taps, n_taps * sizeof(float),
-                  hipMemcpyHostToDevice) != hipSuccess) {
-        set_err("taps upload failed");
-        fsdr_filter_destroy(f);
-        return nullptr;
-    }
-    f->n_taps_padded = (int)n_taps;
+    f->length = f->fir.n_taps = n_taps;
+    f->fir.n_padded = (int)n_taps;
+    f->fir.interp = interp;
+    f->fir.decim = decim;
+    f->item_in = item_in;
+    f->item_out = item_out;
+    if (!upload(f->fir.taps, taps, n_taps, "taps upload failed"))
+        return create_failed(f);
+    return f;
+}
+
+extern "C" fsdr_filter* fsdr_resamp_cf32_create(size_t interp, size_t decim,
+                                                const float* taps,
+                                                size_t n_taps) {
+    fsdr_filter* f =
+        resamp_create(K_RESAMP_CF32, 8, 8, interp, decim, taps, n_taps);
+    /* interp==1, decim==4 (the config-3 "4:1" shape): y[k] =
+     * sum_t x[4k+t]*h[T-1-t] is the decimating FIR evaluated with its
+     * window origin shifted by D-1, so route it to the MFMA decim
+     * kernel with the input pointer rebased (launch site). */
+    if (f && interp == 1 && decim == 4 && n_taps <= 512)
+        f->fir.decim4 = fsdr_decim_fir_cf32_create(4, taps, n_taps);
     return f;
 }
 
 extern "C" fsdr_filter* fsdr_resamp_f32_create(size_t interp, size_t decim,
                                                const float* taps,
                                                size_t n_taps) {
-    fsdr_filter* f =
-        resamp_f32_like_create(K_RESAMP_F32, interp, decim, taps, n_taps);
-    if (f) f->item_in = 4;
-    return f;
-}
-
-/* the carried `last` of the demodulator, (0, 0) on a fresh handle */
-static bool alloc_demod_last(fsdr_filter* f) {
-    if (ensure_dev(&f->d_hist, &f->d_hist_bytes, sizeof(float2)) != FSDR_OK ||
-        hipMemset(f->d_hist, 0, sizeof(float2)) != hipSuccess) {
-        set_err("demodulator state alloc failed");
-        return false;
-    }
-    return true;
+    return resamp_create(K_RESAMP_F32, 4, 4, interp, decim, taps, n_taps);
 }
 
 extern "C" fsdr_filter* fsdr_quad_demod_create(void) {
     fsdr_filter* f = create_common(K_QUAD_DEMOD);
     if (!f) return nullptr;
     f->item_out = 4;
-    f->n_taps = 1; /* length(): an Apply block needs one item */
-    if (!alloc_demod_last(f)) {
-        fsdr_filter_destroy(f);
-        return nullptr;
-    }
+    f->length = 1; /* an Apply block needs one item */
+    if (!alloc_zeroed(f->demod.last, sizeof(float2),
+                      "demodulator state alloc failed"))
+        return create_failed(f);
     return f;
 }
 
@@ -4466,14 +4477,14 @@ extern "C" fsdr_filter* fsdr_fm_demod_resamp_create(size_t interp,
                                                     size_t decim,
                                                     const float* taps,
                                                     size_t n_taps) {
-    fsdr_filter* f = resamp_f32_like_create(K_FM_DEMOD_RESAMP, interp, decim,
-                                            taps, n_taps);
-    if (f && !alloc_demod_last(f)) {
-        fsdr_filter_destroy(f);
-        return nullptr;
-    }
+    fsdr_filter* f =
+        resamp_create(K_FM_DEMOD_RESAMP, 8, 4, interp, decim, taps, n_taps);
+    if (f && !alloc_zeroed(f->demod.last, sizeof(float2),
+                           "demodulator state alloc failed"))
+        return create_failed(f);
     return f;
 }
+
 
 extern "C" fsdr_filter* fsdr_fft_cf32_create(size_t len, int inverse,
                                              int fft_shift,
@@ -4486,16 +4497,16 @@ extern "C" fsdr_filter* fsdr_fft_cf32_create(size_t len, int inverse,
     }
     fsdr_filter* f = create_common(K_FFT_CF32);
     if (!f) return nullptr;
-    f->fft_len = len;
-    f->inverse = inverse;
-    f->fft_shift = fft_shift;
-    f->norm = normalize ? *normalize : 0.f;
-    f->n_taps = len; /* length() = min_items = len (fft.rs:106-109) */
+    f->fft.len = len;
+    f->fft.inverse = inverse;
+    f->fft.shift = fft_shift;
+    f->fft.norm = normalize ? *normalize : 0.f;
+    f->length = len; /* min_items = len (fft.rs:106-109) */
     size_t tlen = len;
     if (!pow2) {
         size_t M = 4;
         while (M < 2 * len - 1) M <<= 1;
-        f->fft_m = M;
+        f->fft.m = M;
         tlen = M; /* twiddles for the M-point passes */
         /* chirp w(k) = e^{sigma*pi*i*k^2/len}, sigma = -1 fwd / +1 inv;
          * k^2 reduced mod 2*len in integers before the f64 angle */
@@ -4537,16 +4548,9 @@ extern "C" fsdr_filter* fsdr_fft_cf32_create(size_t len, int inverse,
             }
             B[k] = make_float2((float)sre, (float)sim);
         }
-        if (hipMalloc(&f->d_chirp, len * sizeof(float2)) != hipSuccess ||
-            hipMemcpy(f->d_chirp, w.data(), len * sizeof(float2),
-                      hipMemcpyHostToDevice) != hipSuccess ||
-            hipMalloc(&f->d_B, M * sizeof(float2)) != hipSuccess ||
-            hipMemcpy(f->d_B, B.data(), M * sizeof(float2),
-                      hipMemcpyHostToDevice) != hipSuccess) {
-            set_err("bluestein table upload failed");
-            fsdr_filter_destroy(f);
-            return nullptr;
-        }
+        if (!upload(f->fft.chirp, w, "bluestein table upload failed") ||
+            !upload(f->fft.B, B, "bluestein table upload failed"))
+            return create_failed(f);
     }
     /* twiddle table W[k] = e^{-2πik/tlen}, k < tlen, computed in f64
      * (radix-4 needs indices up to 3(tlen/4-1)) */
@@ -4555,13 +4559,8 @@ extern "C" fsdr_filter* fsdr_fft_cf32_create(size_t len, int inverse,
         double a = -2.0 * M_PI * (double)k / (double)tlen;
         tw[k] = make_float2((float)cos(a), (float)sin(a));
     }
-    if (hipMalloc(&f->d_twid, tw.size() * sizeof(float2)) != hipSuccess ||
-        hipMemcpy(f->d_twid, tw.data(), tw.size() * sizeof(float2),
-                  hipMemcpyHostToDevice) != hipSuccess) {
-        set_err("twiddle upload failed");
-        fsdr_filter_destroy(f);
-        return nullptr;
-    }
+    if (!upload(f->fft.twid, tw, "twiddle upload failed"))
+        return create_failed(f);
     return f;
 }
 
@@ -4569,6 +4568,7 @@ extern "C" fsdr_filter* fsdr_mag2_create(void) {
     fsdr_filter* f = create_common(K_MAG2);
     if (!f) return nullptr;
     f->item_out = 4;
+    f->length = 1;
     return f;
 }
 
@@ -4584,8 +4584,9 @@ extern "C" fsdr_filter* fsdr_xlating_fir_cf32_create(const float* taps,
     }
     fsdr_filter* f = create_common(K_XLATING);
     if (!f) return nullptr;
-    f->n_taps = n_taps;
-    f->decim = decimation;
+    f->length = f->fir.n_taps = n_taps;
+    f->fir.n_padded = (int)n_taps;
+    f->fir.decim = decimation;
     /* bpf taps, f32 math identical to from_polar (:79-88), stored
      * REVERSED for the kernel */
     std::vector<float2> bpf(n_taps);
@@ -4596,19 +4597,13 @@ extern "C" fsdr_filter* fsdr_xlating_fir_cf32_create(const float* taps,
         bpf[n_taps - 1 - src_i] =
             make_float2(rot.x * taps[src_i], rot.y * taps[src_i]);
     }
-    if (hipMalloc(&f->d_taps, bpf.size() * sizeof(float2)) != hipSuccess ||
-        hipMemcpy(f->d_taps, bpf.data(), bpf.size() * sizeof(float2),
-                  hipMemcpyHostToDevice) != hipSuccess) {
-        set_err("bpf taps upload failed");
-        delete f;
-        return nullptr;
-    }
+    if (!upload(f->fir.taps, bpf, "bpf taps upload failed"))
+        return create_failed(f);
     /* rotator increment (:91-94) and unit start phase (rotator.rs:17-19) */
-    f->theta = -6.2831853071795864769f * offset * (float)decimation /
-               sample_rate;
-    f->rot_re = 1.0f;
-    f->rot_im = 0.0f;
-    f->n_taps_padded = (int)n_taps;
+    f->xlat.theta = -6.2831853071795864769f * offset * (float)decimation /
+                    sample_rate;
+    f->xlat.rot_re = 1.0f;
+    f->xlat.rot_im = 0.0f;
     return f;
 }
 
@@ -4635,12 +4630,12 @@ extern "C" fsdr_filter* fsdr_pfb_channelizer_create(size_t num_channels,
     }
     fsdr_filter* f = create_common(K_PFB);
     if (!f) return nullptr;
-    f->width = num_channels;
+    f->pfb.channels = num_channels;
     /* channelizer.rs:105: decimation_factor = N / oversample_rate */
-    f->decim = (size_t)((float)num_channels / oversample_rate);
+    f->chan.decim = (size_t)((float)num_channels / oversample_rate);
     size_t tpf = (n_taps + num_channels - 1) / num_channels;
-    f->history = tpf;
-    f->n_taps = n_taps;
+    f->pfb.tpf = tpf;
+    f->length = n_taps;
     /* partition_filter_taps (utilities.rs:5-25): part[i][c] = taps[i+c*N],
      * zero-padded */
     std::vector<float> part(num_channels * tpf, 0.f);
@@ -4649,18 +4644,9 @@ extern "C" fsdr_filter* fsdr_pfb_channelizer_create(size_t num_channels,
         for (size_t t = i; t < n_taps; t += num_channels)
             part[i * tpf + cnt++] = taps[t];
     }
-    if (hipMalloc(&f->d_taps, part.size() * sizeof(float)) != hipSuccess ||
-        hipMemcpy(f->d_taps, part.data(), part.size() * sizeof(float),
-                  hipMemcpyHostToDevice) != hipSuccess) {
-        set_err("pfb taps upload failed");
-        delete f;
-        return nullptr;
-    }
-    f->sub = fsdr_fft_cf32_create(num_channels, 1, 0, nullptr);
-    if (!f->sub) {
-        delete f;
-        return nullptr;
-    }
+    if (!upload(f->chan.taps, part, "pfb taps upload failed") ||
+        !(f->pfb.ifft = fsdr_fft_cf32_create(num_channels, 1, 0, nullptr)))
+        return create_failed(f);
     return f;
 }
 
@@ -4765,24 +4751,15 @@ extern "C" fsdr_filter* fsdr_pfb_synthesizer_create(size_t num_channels,
     if (!f) return nullptr;
     const size_t N = num_channels;
     const size_t tpf = (n_taps + N - 1) / N;
-    f->width = N;
-    f->history = tpf;
-    f->n_taps = n_taps;
+    f->pfb.channels = N;
+    f->pfb.tpf = tpf;
+    f->length = n_taps;
     /* partition_filter_taps, transposed: partT[j][c] = taps[c + j*N] */
     std::vector<float> part(N * tpf, 0.f);
     for (size_t t = 0; t < n_taps; t++) part[t] = taps[t];
-    if (hipMalloc(&f->d_taps, part.size() * sizeof(float)) != hipSuccess ||
-        hipMemcpy(f->d_taps, part.data(), part.size() * sizeof(float),
-                  hipMemcpyHostToDevice) != hipSuccess) {
-        set_err("pfb synthesizer taps upload failed");
-        fsdr_filter_destroy(f);
-        return nullptr;
-    }
-    f->sub = fsdr_fft_cf32_create(N, 1, 0, nullptr);
-    if (!f->sub) {
-        fsdr_filter_destroy(f);
-        return nullptr;
-    }
+    if (!upload(f->synth.taps, part, "pfb synthesizer taps upload failed") ||
+        !(f->pfb.ifft = fsdr_fft_cf32_create(N, 1, 0, nullptr)))
+        return create_failed(f);
     return f;
 }
 
@@ -5060,47 +5037,35 @@ extern "C" fsdr_filter* fsdr_pfb_arb_resampler_create(float rate,
     }
     fsdr_filter* f = create_common(K_PFB_ARB);
     if (!f) return nullptr;
-    if (fsdr_pfb_arb_schedule_create(rate, num_filters, &f->arb) != FSDR_OK) {
-        fsdr_filter_destroy(f);
-        return nullptr;
-    }
+    if (fsdr_pfb_arb_schedule_create(rate, num_filters, &f->arb.sched) !=
+        FSDR_OK)
+        return create_failed(f);
+    const fsdr_pfb_arb_schedule* s = f->arb.sched;
     const size_t nf = num_filters, tpf = (n_taps + nf - 1) / nf;
     bool taps_lds;
-    if ((size_t)f->arb->W * f->arb->RL + tpf + 1 > ARB_NV * ARB_BLOCK ||
-        pfb_arb_lds(f->arb, tpf, &taps_lds) > 64 * 1024) {
+    if ((size_t)s->W * s->RL + tpf + 1 > ARB_NV * ARB_BLOCK ||
+        pfb_arb_lds(s, tpf, &taps_lds) > 64 * 1024) {
         set_err("pfb arb resampler: taps per filter too long for the LDS "
                 "tile");
-        fsdr_filter_destroy(f);
-        return nullptr;
+        return create_failed(f);
     }
-    f->width = num_channels;
-    f->history = tpf;
-    f->n_taps = n_taps;
+    f->pfb.channels = num_channels;
+    f->pfb.tpf = tpf;
+    f->length = n_taps;
     /* partition_filter_taps (utilities.rs:5-25), each part reversed */
     std::vector<float> rp(nf * tpf, 0.f);
     for (size_t t = 0; t < n_taps; t++)
         rp[(t % nf) * tpf + (tpf - 1 - t / nf)] = taps[t];
-    const size_t ckb = f->arb->ck.size() * sizeof(ArbCk);
-    const size_t hb = 2 * num_channels * tpf * 8;
-    if (hipMalloc(&f->d_taps, rp.size() * sizeof(float)) != hipSuccess ||
-        hipMemcpy(f->d_taps, rp.data(), rp.size() * sizeof(float),
-                  hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc(&f->d_ck, ckb) != hipSuccess ||
-        hipMemcpy(f->d_ck, f->arb->ck.data(), ckb,
-                  hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc(&f->d_hist, hb) != hipSuccess ||
-        hipMemset(f->d_hist, 0, hb) != hipSuccess) {
-        set_err("pfb arb resampler upload failed");
-        fsdr_filter_destroy(f);
-        return nullptr;
-    }
-    f->d_hist_bytes = hb;
+    const char* err = "pfb arb resampler upload failed";
+    if (!upload(f->arb.taps, rp, err) || !upload(f->arb.ck, s->ck, err) ||
+        !alloc_zeroed(f->arb.window.buf, 2 * num_channels * tpf * 8, err))
+        return create_failed(f);
     return f;
 }
 
 extern "C" const fsdr_pfb_arb_schedule* fsdr_pfb_arb_resampler_schedule(
     const fsdr_filter* f) {
-    return f && f->kind == K_PFB_ARB ? f->arb : nullptr;
+    return f && f->kind == K_PFB_ARB ? f->arb.sched : nullptr;
 }
 
 /* ---- IIR plan: the constant matrices of the blocked recurrence -------- */
@@ -5236,32 +5201,22 @@ extern "C" fsdr_filter* fsdr_iir_f32_create(const float* a, size_t n_a,
     if (fsdr_iir_plan_create(a, n_a, &plan) != FSDR_OK) return nullptr;
     fsdr_filter* f = create_common(K_IIR_F32);
     if (!f) { delete plan; return nullptr; }
-    f->iir = plan;
-    f->n_taps = n_b;
+    f->iir.plan = plan;
+    f->length = f->iir.n_b = n_b;
     f->item_in = f->item_out = 4;
     std::vector<float> tb(plan->H);
     tb.insert(tb.end(), plan->pc.begin(), plan->pc.end());
     tb.insert(tb.end(), plan->pt.begin(), plan->pt.end());
-    const size_t hb = 2 * IIR_NA_MAX * sizeof(float);
-    if (hipMalloc(&f->d_taps, n_b * sizeof(float)) != hipSuccess ||
-        hipMemcpy(f->d_taps, b, n_b * sizeof(float),
-                  hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc(&f->d_ck, (tb.size() + 1) * sizeof(float)) != hipSuccess ||
-        (tb.size() &&
-         hipMemcpy(f->d_ck, tb.data(), tb.size() * sizeof(float),
-                   hipMemcpyHostToDevice) != hipSuccess) ||
-        hipMalloc(&f->d_hist, hb) != hipSuccess ||
-        hipMemset(f->d_hist, 0, hb) != hipSuccess) {
-        set_err("iir upload failed");
-        fsdr_filter_destroy(f);
-        return nullptr;
-    }
-    f->d_hist_bytes = hb;
+    tb.push_back(0.f); /* no feedback: the tables are empty */
+    const char* err = "iir upload failed";
+    if (!upload(f->iir.b, b, n_b, err) || !upload(f->iir.tables, tb, err) ||
+        !alloc_zeroed(f->iir.mem.buf, 2 * IIR_NA_MAX * sizeof(float), err))
+        return create_failed(f);
     return f;
 }
 
 extern "C" const fsdr_iir_plan* fsdr_iir_plan_of(const fsdr_filter* f) {
-    return f && f->kind == K_IIR_F32 ? f->iir : nullptr;
+    return f && f->kind == K_IIR_F32 ? f->iir.plan : nullptr;
 }
 
 /* ---- LoRa FFT demodulator: tables, counts, handle --------------------- */
@@ -5328,11 +5283,11 @@ extern "C" int fsdr_lora_demod_count(unsigned sf, size_t n_in, size_t n_out,
 
 static int lora_upload_chirp(fsdr_filter* f, long long cfo_int,
                              double cfo_frac) {
-    std::vector<fsdr_cf32> t(f->fft_len);
-    lora_downchirp_table(f->lora_sf, f->lora_mode == LORA_RAW, cfo_int,
+    std::vector<fsdr_cf32> t((size_t)1 << f->lora.sf);
+    lora_downchirp_table(f->lora.sf, f->lora.mode == LORA_RAW, cfo_int,
                          cfo_frac, t.data());
-    HIP_TRY(hipMemcpy(f->d_chirp, t.data(), t.size() * sizeof(fsdr_cf32),
-                      hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(f->lora.chirp.ptr, t.data(),
+                      t.size() * sizeof(fsdr_cf32), hipMemcpyHostToDevice));
     return FSDR_OK;
 }
 
@@ -5348,24 +5303,21 @@ extern "C" fsdr_filter* fsdr_lora_demod_create(unsigned sf, int mode) {
     fsdr_filter* f = create_common(K_LORA_DEMOD);
     if (!f) return nullptr;
     const size_t n = (size_t)1 << sf;
-    f->lora_sf = sf;
-    f->lora_mode = mode;
-    f->fft_len = n;
-    f->n_taps = n; /* length() = set_min_items(N), fft_demod.rs:269 */
+    f->lora.sf = sf;
+    f->lora.mode = mode;
+    f->length = n; /* set_min_items(N), fft_demod.rs:269 */
     f->item_out = mode == LORA_SOFT ? LORA_MAX_SF * sizeof(double) : 2;
     std::vector<float2> tw(n);
     for (size_t k = 0; k < n; k++) {
         const double a = -2.0 * M_PI * (double)k / (double)n;
         tw[k] = make_float2((float)cos(a), (float)sin(a));
     }
-    if (hipMalloc(&f->d_twid, n * sizeof(float2)) != hipSuccess ||
-        hipMemcpy(f->d_twid, tw.data(), n * sizeof(float2),
-                  hipMemcpyHostToDevice) != hipSuccess ||
-        hipMalloc(&f->d_chirp, n * sizeof(float2)) != hipSuccess ||
+    const char* err = "lora table upload failed";
+    if (!upload(f->lora.twid, tw, err) ||
+        f->lora.chirp.ensure(n * sizeof(float2)) != hipSuccess ||
         lora_upload_chirp(f, 0, 0.0) != FSDR_OK) {
-        set_err("lora table upload failed");
-        fsdr_filter_destroy(f);
-        return nullptr;
+        set_err(err);
+        return create_failed(f);
     }
     return f;
 }
@@ -5377,7 +5329,7 @@ extern "C" int fsdr_lora_demod_set_frame(fsdr_filter* f, long long cfo_int,
         set_err("not a lora demodulator");
         return FSDR_ERR_INVALID;
     }
-    f->lora_reduced = reduced_rate != 0;
+    f->lora.reduced = reduced_rate != 0;
     return lora_upload_chirp(f, cfo_int, cfo_frac);
 }
 
@@ -5392,22 +5344,19 @@ extern "C" fsdr_filter* fsdr_moving_avg_create(size_t width,
     }
     fsdr_filter* f = create_common(K_MOVAVG);
     if (!f) return nullptr;
-    f->width = width;
-    f->history = history;
-    f->decay = decay_factor;
+    f->movavg.width = width;
+    f->movavg.history = history;
+    f->movavg.decay = decay_factor;
     f->item_in = f->item_out = 4;
-    f->n_taps = width; /* length() = min_items analogue */
-    if (hipMalloc(&f->d_avg, width * sizeof(float)) != hipSuccess ||
-        hipMemset(f->d_avg, 0, width * sizeof(float)) != hipSuccess) {
-        set_err("avg state alloc failed");
-        delete f;
-        return nullptr;
-    }
+    f->length = width; /* min_items analogue */
+    if (!alloc_zeroed(f->movavg.avg, width * sizeof(float),
+                      "avg state alloc failed"))
+        return create_failed(f);
     return f;
 }
 
 extern "C" size_t fsdr_filter_length(const fsdr_filter* f) {
-    return f ? (f->kind == K_MAG2 ? 1 : f->n_taps) : 0;
+    return f ? f->length : 0;
 }
 
 /* Which kernel instantiation the handle's launches select (the
@@ -5416,15 +5365,10 @@ extern "C" size_t fsdr_filter_length(const fsdr_filter* f) {
 extern "C" int fsdr_filter_variant(const fsdr_filter* f, int* kk_mfma,
                                    int* kk_mfma32, int* tp_tpl) {
     if (!f) { set_err("null filter"); return FSDR_ERR_INVALID; }
-    int kk = f->kk_mfma, kk32 = f->kk_mfma32, tp = f->tp_tpl;
-    if (f->kind == K_RESAMP_CF32) {
-        kk = f->sub ? f->sub->kk_mfma : 0;
-        kk32 = f->sub ? f->sub->kk_mfma32 : 0;
-        tp = f->sub ? f->sub->tp_tpl : 0;
-    }
-    if (kk_mfma) *kk_mfma = kk;
-    if (kk_mfma32) *kk_mfma32 = kk32;
-    if (tp_tpl) *tp_tpl = tp;
+    if (f->kind == K_RESAMP_CF32 && f->fir.decim4) f = f->fir.decim4;
+    if (kk_mfma) *kk_mfma = f->fir.kk_mfma;
+    if (kk_mfma32) *kk_mfma32 = f->fir.kk_mfma32;
+    if (tp_tpl) *tp_tpl = f->fir.tp_tpl;
     return FSDR_OK;
 }
 
@@ -5436,26 +5380,15 @@ extern "C" size_t fsdr_filter_item_sizes(const fsdr_filter* f,
     return f->item_in;
 }
 
+fsdr_filter::~fsdr_filter() {
+    delete fir.decim4;
+    delete pfb.ifft;
+    delete arb.sched;
+    delete iir.plan;
+}
+
 extern "C" void fsdr_filter_destroy(fsdr_filter* f) {
-    if (!f) return;
-    if (f->sub) fsdr_filter_destroy(f->sub);
-    if (f->d_avg) (void)hipFree(f->d_avg);
-    if (f->d_taps) (void)hipFree(f->d_taps);
-    if (f->d_rtaps) (void)hipFree(f->d_rtaps);
-    if (f->d_mtaps) (void)hipFree(f->d_mtaps);
-    if (f->d_mtaps32) (void)hipFree(f->d_mtaps32);
-    if (f->d_twid) (void)hipFree(f->d_twid);
-    if (f->d_chirp) (void)hipFree(f->d_chirp);
-    if (f->d_B) (void)hipFree(f->d_B);
-    if (f->d_in) (void)hipFree(f->d_in);
-    if (f->d_out) (void)hipFree(f->d_out);
-    if (f->d_scratch) (void)hipFree(f->d_scratch);
-    if (f->d_hist) (void)hipFree(f->d_hist);
-    if (f->d_early) (void)hipFree(f->d_early);
-    if (f->d_ck) (void)hipFree(f->d_ck);
-    fsdr_pfb_arb_schedule_destroy(f->arb);
-    fsdr_iir_plan_destroy(f->iir);
-    delete f;
+    if (f) delete f;
 }
 
 /* ---- kernel launch helpers ---- */
@@ -5570,23 +5503,23 @@ static int launch_fir_cf32(fsdr_filter* f, const void* d_in, void* d_out,
      * stalls all 4 waves of the block at each staging barrier) */
     long long cap = grid_cap(256 * 16);
     int grid = (int)std::min<long long>(tiles, cap);
-    const char* mf32 = getenv("FSDR_FIR_MFMA32");
-    if (f->kk_mfma && mf32 && atoi(mf32) != 0) {
+    if (f->fir.kk_mfma && env_int("FSDR_FIR_MFMA32", 0) != 0) {
         /* 32x32 variant reuses d_mtaps when kk32 <= allocated; host
          * uploads a separate array sized for K = T+31 */
         long long tiles32 =
             ((long long)n_out + MFIR32_TILE - 1) / MFIR32_TILE;
         long long cap32 = grid_cap(256 * 64);
         int grid32 = (int)std::min<long long>(tiles32, cap32);
-        unsigned elems32 = MFIR32_TILE + f->kk_mfma32 + 8;
+        unsigned elems32 = MFIR32_TILE + f->fir.kk_mfma32 + 8;
         size_t lds32 = (2 * (size_t)((elems32 + 31u) & ~31u) +
-                        f->kk_mfma32 + 36) * sizeof(float);
-        if (!tpl_dispatch(fir_mfma32_ks{}, f->kk_mfma32, [&](auto K) {
+                        f->fir.kk_mfma32 + 36) * sizeof(float);
+        if (!tpl_dispatch(fir_mfma32_ks{}, f->fir.kk_mfma32, [&](auto K) {
                 hipLaunchKernelGGL(
                     HIP_KERNEL_NAME(k_fir_mfma32_tpl<decltype(K)::value>),
                     dim3(grid32), dim3(MFIR32_BLOCK), lds32, st,
-                    (const float2*)d_in, (float2*)d_out, f->d_mtaps32,
-                    (long long)n_out, (long long)n_in);
+                    (const float2*)d_in, (float2*)d_out,
+                    f->fir.mtaps32.as<float>(), (long long)n_out,
+                    (long long)n_in);
             })) {
             set_err("bad mfma32 K");
             return FSDR_ERR_INVALID;
@@ -5594,17 +5527,17 @@ static int launch_fir_cf32(fsdr_filter* f, const void* d_in, void* d_out,
         HIP_TRY(hipGetLastError());
         return FSDR_OK;
     }
-    const char* mf = getenv("FSDR_FIR_MFMA");
-    if (f->kk_mfma && (!mf || atoi(mf) != 0)) {
-        unsigned elems = MFIR_TILE + f->kk_mfma + 8;
-        size_t lds = (2 * (size_t)((elems + 31u) & ~31u) + f->kk_mfma + 20)
+    if (f->fir.kk_mfma && env_on("FSDR_FIR_MFMA")) {
+        unsigned elems = MFIR_TILE + f->fir.kk_mfma + 8;
+        size_t lds = (2 * (size_t)((elems + 31u) & ~31u) + f->fir.kk_mfma + 20)
                      * sizeof(float);
-        if (!tpl_dispatch(fir_mfma_ks{}, f->kk_mfma, [&](auto K) {
+        if (!tpl_dispatch(fir_mfma_ks{}, f->fir.kk_mfma, [&](auto K) {
                 hipLaunchKernelGGL(
                     HIP_KERNEL_NAME(k_fir_mfma_tpl<decltype(K)::value>),
                     dim3(grid), dim3(MFIR_BLOCK), lds, st,
-                    (const float2*)d_in, (float2*)d_out, f->d_mtaps,
-                    (long long)n_out, (long long)n_in);
+                    (const float2*)d_in, (float2*)d_out,
+                    f->fir.mtaps.as<float>(), (long long)n_out,
+                    (long long)n_in);
             })) {
             set_err("bad mfma K");
             return FSDR_ERR_INVALID;
@@ -5612,16 +5545,17 @@ static int launch_fir_cf32(fsdr_filter* f, const void* d_in, void* d_out,
         HIP_TRY(hipGetLastError());
         return FSDR_OK;
     }
-    if (f->tp_tpl) {
-        unsigned elems = FIR_TILE_OUT + f->tp_tpl + 8;
-        size_t lds = (2 * (size_t)((elems + 7u) & ~7u) + f->tp_tpl + 3) *
+    if (f->fir.tp_tpl) {
+        unsigned elems = FIR_TILE_OUT + f->fir.tp_tpl + 8;
+        size_t lds = (2 * (size_t)((elems + 7u) & ~7u) + f->fir.tp_tpl + 3) *
                      sizeof(float);
-        if (!tpl_dispatch(fir_tpl_tps{}, f->tp_tpl, [&](auto TP) {
+        if (!tpl_dispatch(fir_tpl_tps{}, f->fir.tp_tpl, [&](auto TP) {
                 hipLaunchKernelGGL(
                     HIP_KERNEL_NAME(k_fir_cf32_tpl<decltype(TP)::value>),
                     dim3(grid), dim3(FIR_BLOCK), lds, st,
-                    (const float2*)d_in, (float2*)d_out, f->d_rtaps,
-                    (long long)n_out, (long long)n_in);
+                    (const float2*)d_in, (float2*)d_out,
+                    f->fir.rtaps.as<float>(), (long long)n_out,
+                    (long long)n_in);
             })) {
             set_err("bad template tap count");
             return FSDR_ERR_INVALID;
@@ -5629,30 +5563,38 @@ static int launch_fir_cf32(fsdr_filter* f, const void* d_in, void* d_out,
         HIP_TRY(hipGetLastError());
         return FSDR_OK;
     }
-    unsigned elems = FIR_TILE_OUT + f->n_taps_padded - 1 + 6;
-    size_t lds = (2 * (size_t)plane_floats(elems) + f->n_taps_padded + 4) *
+    unsigned elems = FIR_TILE_OUT + f->fir.n_padded - 1 + 6;
+    size_t lds = (2 * (size_t)plane_floats(elems) + f->fir.n_padded + 4) *
                  sizeof(float);
     hipLaunchKernelGGL(k_fir_cf32, dim3(grid), dim3(FIR_BLOCK), lds, st,
-                       (const float2*)d_in, (float2*)d_out, f->d_taps,
-                       f->n_taps_padded, (long long)n_out, (long long)n_in);
+                       (const float2*)d_in, (float2*)d_out,
+                       f->fir.taps.as<float>(), f->fir.n_padded,
+                       (long long)n_out, (long long)n_in);
     HIP_TRY(hipGetLastError());
     return FSDR_OK;
+}
+
+static int run_fir_cf32(fsdr_filter* f, const void* d_in, size_t n_in,
+                        void* d_out, size_t n_out, void* stream,
+                        fsdr_filter_result* r) {
+    hipStream_t st = (hipStream_t)stream;
+    *r = fir_status(n_in, f->fir.n_taps, n_out);
+    return launch_fir_cf32(f, d_in, d_out, r->produced, n_in, st);
 }
 
 static int launch_decim_cf32(fsdr_filter* f, const void* d_in, void* d_out,
                              size_t n_out, size_t n_in, hipStream_t st) {
     if (n_out == 0) return FSDR_OK;
-    const char* dmf = getenv("FSDR_DECIM_MFMA");
-    if (f->decim == 4 && f->kk_mfma && (!dmf || atoi(dmf) != 0)) {
+    if (f->fir.decim == 4 && f->fir.kk_mfma && env_on("FSDR_DECIM_MFMA")) {
         long long tiles = ((long long)n_out + MDFIR_TILE - 1) / MDFIR_TILE;
         long long cap = grid_cap(256 * 64);
         int grid = (int)std::min<long long>(tiles, cap);
-        if (!tpl_dispatch(decim4_mfma_ks{}, f->kk_mfma, [&](auto K) {
+        if (!tpl_dispatch(decim4_mfma_ks{}, f->fir.kk_mfma, [&](auto K) {
                 using G = ChainGeom<decltype(K)::value>;
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_decim4_mfma_tpl<G::KKD>),
                                    dim3(grid), dim3(G::BLOCK),
                                    G::halves_bytes, st, (const float2*)d_in,
-                                   (float2*)d_out, f->d_mtaps,
+                                   (float2*)d_out, f->fir.mtaps.as<float>(),
                                    (long long)n_out, (long long)n_in);
             })) {
             set_err("bad decim mfma K");
@@ -5661,18 +5603,19 @@ static int launch_decim_cf32(fsdr_filter* f, const void* d_in, void* d_out,
         HIP_TRY(hipGetLastError());
         return FSDR_OK;
     }
-    if (f->decim == 4 && f->tp_tpl) {
+    if (f->fir.decim == 4 && f->fir.tp_tpl) {
         long long tiles = ((long long)n_out + DFIRT_TILE - 1) / DFIRT_TILE;
         long long cap = grid_cap(256 * 64);
         int grid = (int)std::min<long long>(tiles, cap);
-        size_t lds = (4 * (size_t)dfirt_sp(f->tp_tpl) +
-                      4 * ((size_t)f->tp_tpl + 4)) * sizeof(float);
-        if (!tpl_dispatch(decim4_tpl_tpds{}, f->tp_tpl, [&](auto TPD) {
+        size_t lds = (4 * (size_t)dfirt_sp(f->fir.tp_tpl) +
+                      4 * ((size_t)f->fir.tp_tpl + 4)) * sizeof(float);
+        if (!tpl_dispatch(decim4_tpl_tpds{}, f->fir.tp_tpl, [&](auto TPD) {
                 hipLaunchKernelGGL(
                     HIP_KERNEL_NAME(k_fir_decim4_tpl<decltype(TPD)::value>),
                     dim3(grid), dim3(DFIRT_BLOCK), lds, st,
-                    (const float2*)d_in, (float2*)d_out, f->d_rtaps,
-                    (long long)n_out, (long long)n_in);
+                    (const float2*)d_in, (float2*)d_out,
+                    f->fir.rtaps.as<float>(), (long long)n_out,
+                    (long long)n_in);
             })) {
             set_err("bad decim template tap count");
             return FSDR_ERR_INVALID;
@@ -5680,28 +5623,36 @@ static int launch_decim_cf32(fsdr_filter* f, const void* d_in, void* d_out,
         HIP_TRY(hipGetLastError());
         return FSDR_OK;
     }
-    if (f->decim == 4) {
-        unsigned elems = DFIR_TILE_OUT * 4 + f->n_taps_padded - 1 + 20;
-        size_t lds = (2 * (size_t)plane_floats(elems) + f->n_taps_padded + 4)
+    if (f->fir.decim == 4) {
+        unsigned elems = DFIR_TILE_OUT * 4 + f->fir.n_padded - 1 + 20;
+        size_t lds = (2 * (size_t)plane_floats(elems) + f->fir.n_padded + 4)
                      * sizeof(float);
         long long tiles =
             ((long long)n_out + DFIR_TILE_OUT - 1) / DFIR_TILE_OUT;
         int grid = (int)std::min<long long>(tiles, grid_cap(256 * 8));
         hipLaunchKernelGGL(k_fir_decim4_cf32, dim3(grid), dim3(DFIR_BLOCK),
                            lds, st, (const float2*)d_in, (float2*)d_out,
-                           f->d_taps, f->n_taps_padded, (long long)n_out,
-                           (long long)n_in);
+                           f->fir.taps.as<float>(), f->fir.n_padded,
+                           (long long)n_out, (long long)n_in);
     } else {
         hipLaunchKernelGGL(k_fir_decim_generic_cf32,
                            dim3(grid_for((long long)n_out, 256)), dim3(256),
                            0, st, (const float2*)d_in, (float2*)d_out,
-                           f->d_taps,
-                           f->n_taps_padded, /* == n_taps for generic */
-                           (long long)f->decim, (long long)n_out,
+                           f->fir.taps.as<float>(),
+                           f->fir.n_padded, /* == n_taps for generic */
+                           (long long)f->fir.decim, (long long)n_out,
                            (long long)n_in);
     }
     HIP_TRY(hipGetLastError());
     return FSDR_OK;
+}
+
+static int run_decim_cf32(fsdr_filter* f, const void* d_in, size_t n_in,
+                          void* d_out, size_t n_out, void* stream,
+                          fsdr_filter_result* r) {
+    hipStream_t st = (hipStream_t)stream;
+    *r = decim_status(f->fir.decim, n_in, f->fir.n_taps, n_out);
+    return launch_decim_cf32(f, d_in, d_out, r->produced, n_in, st);
 }
 
 static int launch_stockham(const float2* d_in, float2* d_out,
@@ -5710,9 +5661,7 @@ static int launch_stockham(const float2* d_in, float2* d_out,
                            float norm, hipStream_t st) {
     int log2n = 0;
     while ((1 << log2n) < n) log2n++;
-    int fpb_base = 1024;
-    if (const char* e = getenv("FSDR_FFT_FPB_BASE")) fpb_base = atoi(e);
-    int fpb = fpb_base / n;
+    int fpb = env_int("FSDR_FFT_FPB_BASE", 1024) / n;
     if (fpb < 1) fpb = 1;
     if (fpb > 16) fpb = 16;
     size_t lds = 2 * (size_t)fpb * n * sizeof(float2);
@@ -5729,42 +5678,55 @@ static int launch_fft(fsdr_filter* f, const void* d_in, void* d_out,
                       size_t frames, hipStream_t st,
                       float* d_mag = nullptr) {
     if (frames == 0) return FSDR_OK;
-    int n = (int)f->fft_len;
-    if (f->fft_m) { /* Bluestein: pre -> FFT_M -> *B -> IFFT_M -> post */
-        int M = (int)f->fft_m;
-        int rc = ensure_dev(&f->d_scratch, &f->d_scratch_bytes,
-                            2 * frames * (size_t)M * sizeof(float2));
-        if (rc) return rc;
-        float2* s1 = (float2*)f->d_scratch;
+    int n = (int)f->fft.len;
+    if (f->fft.m) { /* Bluestein: pre -> FFT_M -> *B -> IFFT_M -> post */
+        int M = (int)f->fft.m;
+        HIP_TRY(f->fft.work.ensure(2 * frames * (size_t)M * sizeof(float2)));
+        float2* s1 = f->fft.work.as<float2>();
         float2* s2 = s1 + frames * (size_t)M;
+        const float2* twid = f->fft.twid.as<float2>();
         long long tM = (long long)frames * M;
         hipLaunchKernelGGL(k_bluestein_pre, dim3(grid_for(tM, 256)),
                            dim3(256), 0, st, (const float2*)d_in, s1,
-                           f->d_chirp, n, M, (long long)frames,
-                           f->inverse && f->fft_shift);
+                           f->fft.chirp.as<float2>(), n, M, (long long)frames,
+                           f->fft.inverse && f->fft.shift);
         HIP_TRY(hipGetLastError());
-        rc = launch_stockham(s1, s2, nullptr, f->d_twid, M, frames, 0, 0,
-                             0.f, st);
+        int rc =
+            launch_stockham(s1, s2, nullptr, twid, M, frames, 0, 0, 0.f, st);
         if (rc) return rc;
         hipLaunchKernelGGL(k_bluestein_mul, dim3(grid_for(tM, 256)),
-                           dim3(256), 0, st, s2, f->d_B, M,
+                           dim3(256), 0, st, s2, f->fft.B.as<float2>(), M,
                            (long long)frames);
         HIP_TRY(hipGetLastError());
-        rc = launch_stockham(s2, s1, nullptr, f->d_twid, M, frames, 1, 0,
-                             0.f, st);
+        rc = launch_stockham(s2, s1, nullptr, twid, M, frames, 1, 0, 0.f, st);
         if (rc) return rc;
-        float scale = (1.0f / (float)M) * (f->norm != 0.f ? f->norm : 1.f);
+        float scale =
+            (1.0f / (float)M) * (f->fft.norm != 0.f ? f->fft.norm : 1.f);
         hipLaunchKernelGGL(k_bluestein_post,
                            dim3(grid_for((long long)frames * n, 256)),
                            dim3(256), 0, st, s1, (float2*)d_out, d_mag,
-                           f->d_chirp, n, M, (long long)frames,
-                           (!f->inverse) && f->fft_shift, scale);
+                           f->fft.chirp.as<float2>(), n, M, (long long)frames,
+                           (!f->fft.inverse) && f->fft.shift, scale);
         HIP_TRY(hipGetLastError());
         return FSDR_OK;
     }
     return launch_stockham((const float2*)d_in, (float2*)d_out, d_mag,
-                           f->d_twid, n, frames, f->inverse, f->fft_shift,
-                           f->norm, st);
+                           f->fft.twid.as<float2>(), n, frames,
+                           f->fft.inverse, f->fft.shift, f->fft.norm, st);
+}
+
+static int run_fft(fsdr_filter* f, const void* d_in, size_t n_in,
+                   void* d_out, size_t n_out, void* stream,
+                   fsdr_filter_result* r) {
+    hipStream_t st = (hipStream_t)stream;
+    /* fft.rs:169-171 */
+    size_t m = n_in < n_out ? n_in : n_out;
+    m = (m / f->fft.len) * f->fft.len;
+    size_t cap = f->fft.len * 32;
+    if (m > cap) m = cap;
+    r->consumed = r->produced = m;
+    r->status = FSDR_BOTH_SUFFICIENT;
+    return launch_fft(f, d_in, d_out, m / f->fft.len, st);
 }
 
 /* Bulk batch FFT: the GPU-native many-frames path (what the chain uses
@@ -5788,12 +5750,13 @@ extern "C" int fsdr_fft_bulk_dev(fsdr_filter* f, const void* d_in,
 /* Input span of one RS_TILE-output tile, and whether one padded f32 plane
  * of it plus the taps fits the 64 KiB the tiled kernels ask for. */
 static bool resamp_f32_tile(const fsdr_filter* f, int* span, size_t* lds) {
-    const size_t tpp = f->n_taps / f->interp;
-    const size_t s = (size_t)(RS_TILE - 1) * f->decim / f->interp + tpp + 2;
-    if (s > (1u << 20) || f->n_taps > (1u << 20) || f->decim > (1u << 21))
+    const size_t nt = f->fir.n_taps, L = f->fir.interp, D = f->fir.decim;
+    const size_t tpp = nt / L;
+    const size_t s = (size_t)(RS_TILE - 1) * D / L + tpp + 2;
+    if (s > (1u << 20) || nt > (1u << 20) || D > (1u << 21))
         return false; /* also keeps the kernels' 32-bit tile indices exact */
     *span = (int)s;
-    *lds = ((size_t)plane_floats((unsigned)s) + f->n_taps) * sizeof(float);
+    *lds = ((size_t)plane_floats((unsigned)s) + nt) * sizeof(float);
     return *lds <= 64 * 1024;
 }
 
@@ -5803,26 +5766,36 @@ static int launch_resamp_f32(const fsdr_filter* f, const float* d_in,
     if (produced == 0) return FSDR_OK;
     int span = 0;
     size_t lds_t = 0;
-    const char* rt = getenv("FSDR_RESAMP_TILED");
-    if (resamp_f32_tile(f, &span, &lds_t) && (!rt || atoi(rt) != 0)) {
+    if (resamp_f32_tile(f, &span, &lds_t) && env_on("FSDR_RESAMP_TILED")) {
         long long tiles = ((long long)produced + RS_TILE - 1) / RS_TILE;
         int grid = (int)std::min<long long>(tiles, grid_cap(256 * 64));
-        auto kern = f->decim % 2 ? k_resamp_tiled_f32<false>
-                                 : k_resamp_tiled_f32<true>;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(RS_BLOCK),
-                           lds_t, st, d_in, d_out, f->d_taps, (int)f->n_taps,
-                           (int)f->interp, (int)f->decim,
+        auto kern = f->fir.decim % 2 ? k_resamp_tiled_f32<false>
+                                     : k_resamp_tiled_f32<true>;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(RS_BLOCK), lds_t, st, d_in,
+                           d_out, f->fir.taps.as<float>(), (int)f->fir.n_taps,
+                           (int)f->fir.interp, (int)f->fir.decim,
                            (long long)produced, (long long)n_in, span);
         HIP_TRY(hipGetLastError());
         return FSDR_OK;
     }
     hipLaunchKernelGGL(k_resamp_f32,
                        dim3(grid_for((long long)produced, 256)), dim3(256),
-                       f->n_taps * sizeof(float), st, d_in, d_out, f->d_taps,
-                       (int)f->n_taps, (int)f->interp, (int)f->decim,
+                       f->fir.n_taps * sizeof(float), st, d_in, d_out,
+                       f->fir.taps.as<float>(), (int)f->fir.n_taps,
+                       (int)f->fir.interp, (int)f->fir.decim,
                        (long long)produced);
     HIP_TRY(hipGetLastError());
     return FSDR_OK;
+}
+
+static int run_resamp_f32(fsdr_filter* f, const void* d_in, size_t n_in,
+                          void* d_out, size_t n_out, void* stream,
+                          fsdr_filter_result* r) {
+    hipStream_t st = (hipStream_t)stream;
+    *r = resamp_status(f->fir.interp, f->fir.decim, f->fir.n_taps, n_in,
+                       n_out);
+    return launch_resamp_f32(f, (const float*)d_in, (float*)d_out,
+                             r->produced, n_in, st);
 }
 
 /* Symbols per block of the LoRa kernel, like the Stockham kernel's frames
@@ -5835,7 +5808,7 @@ static int lora_spb(unsigned sf) {
 static int launch_lora(const fsdr_filter* f, const void* d_in, void* d_out,
                        size_t n_sym, hipStream_t st) {
     if (n_sym == 0) return FSDR_OK;
-    const int n = 1 << f->lora_sf, spb = lora_spb(f->lora_sf);
+    const int n = 1 << f->lora.sf, spb = lora_spb(f->lora.sf);
     const size_t lds = 2 * (size_t)spb * n * sizeof(float2) +
                        LORA_RED_DOUBLES * sizeof(double);
     const long long batches = ((long long)n_sym + spb - 1) / spb;
@@ -5852,9 +5825,9 @@ static int launch_lora(const fsdr_filter* f, const void* d_in, void* d_out,
         }                                                                    \
         hipLaunchKernelGGL((k_lora_demod<MODE_, E_>), dim3(grid),            \
                            dim3(LORA_BLOCK), lds, st, (const float2*)d_in,   \
-                           d_out, (const float2*)f->d_chirp,                 \
-                           (const float2*)f->d_twid, (int)f->lora_sf, spb,   \
-                           f->lora_reduced, (long long)n_sym);               \
+                           d_out, f->lora.chirp.as<const float2>(),          \
+                           f->lora.twid.as<const float2>(), (int)f->lora.sf, \
+                           spb, f->lora.reduced, (long long)n_sym);          \
     } while (0)
 #define LORA_LAUNCH_E(MODE_)                                                 \
     switch (n * spb / LORA_BLOCK) {                                          \
@@ -5863,7 +5836,7 @@ static int launch_lora(const fsdr_filter* f, const void* d_in, void* d_out,
         case 8: LORA_LAUNCH(MODE_, 8); break;                                \
         default: LORA_LAUNCH(MODE_, 16); break;                              \
     }
-    switch (f->lora_mode) {
+    switch (f->lora.mode) {
         case LORA_RAW: LORA_LAUNCH_E(LORA_RAW); break;
         case LORA_HARD: LORA_LAUNCH_E(LORA_HARD); break;
         default: LORA_LAUNCH_E(LORA_SOFT); break;
@@ -5874,7 +5847,15 @@ static int launch_lora(const fsdr_filter* f, const void* d_in, void* d_out,
     return FSDR_OK;
 }
 
-/* `last` <- d_in[consumed-1], ordered after the kernel that read it */
+static int run_lora(fsdr_filter* f, const void* d_in, size_t n_in,
+                    void* d_out, size_t n_out, void* stream,
+                    fsdr_filter_result* r) {
+    hipStream_t st = (hipStream_t)stream;
+    /* whole symbols only: a trailing partial one stays unconsumed */
+    *r = decim_status((size_t)1 << f->lora.sf, n_in, 1, n_out);
+    return launch_lora(f, d_in, d_out, r->produced, st);
+}
+
 /* n > 0 outputs of the IIR from the live memory half; the new memory goes
  * to the other half. Up to three launches (no feedback: one; one tile:
  * no tile-state pass). */
@@ -5882,10 +5863,10 @@ template <int NA>
 static int launch_iir_na(fsdr_filter* f, const float* d_in, float* d_out,
                          long long n, hipStream_t st) {
     const long long n_tiles = (n + IIR_TILE - 1) / IIR_TILE;
-    const int nb = (int)f->n_taps;
-    const float* b = f->d_taps;
+    const int nb = (int)f->iir.n_b;
+    const float* b = f->iir.b.as<float>();
     IirA a = {};
-    for (int q = 0; q < NA; q++) a.a[q] = f->iir->a[q];
+    for (int q = 0; q < NA; q++) a.a[q] = f->iir.plan->a[q];
     const int grid = (int)std::min<long long>(n_tiles, grid_cap(256 * 8));
     if constexpr (NA == 0) {
         hipLaunchKernelGGL(k_iir_apply<0>, dim3(grid), dim3(IIR_BLOCK), 0, st,
@@ -5894,16 +5875,15 @@ static int launch_iir_na(fsdr_filter* f, const float* d_in, float* d_out,
         HIP_TRY(hipGetLastError());
         return FSDR_OK;
     } else {
-        int rc = ensure_dev(&f->d_scratch, &f->d_scratch_bytes,
-                            (size_t)(2 * n_tiles) * NA * sizeof(float));
-        if (rc) return rc;
-        float* T = (float*)f->d_scratch;
+        HIP_TRY(f->iir.tile_states.ensure(
+            (size_t)(2 * n_tiles) * NA * sizeof(float)));
+        float* T = f->iir.tile_states.as<float>();
         float* S = T + n_tiles * NA;
-        const float* H = (const float*)f->d_ck;
+        const float* H = f->iir.tables.as<const float>();
         const float* pc = H + IIR_L * NA;
         const float* pt = pc + IIR_LEVELS * NA * NA;
-        float* mem = (float*)f->d_hist + f->i_state * IIR_NA_MAX;
-        float* mem_new = (float*)f->d_hist + (f->i_state ^ 1) * IIR_NA_MAX;
+        float* mem = f->iir.mem.live<float>(IIR_NA_MAX);
+        float* mem_new = f->iir.mem.next<float>(IIR_NA_MAX);
         if (n_tiles > 1) {
             const int g = (int)std::min<long long>(n_tiles - 1,
                                                    grid_cap(256 * 8));
@@ -5919,14 +5899,14 @@ static int launch_iir_na(fsdr_filter* f, const float* d_in, float* d_out,
                            d_in, d_out, (const float*)S, mem_new, b, nb, a, H,
                            pc, n, n_tiles);
         HIP_TRY(hipGetLastError());
-        f->i_state ^= 1;
+        f->iir.mem.flip();
         return FSDR_OK;
     }
 }
 
 static int launch_iir(fsdr_filter* f, const float* d_in, float* d_out,
                       long long n, hipStream_t st) {
-    switch (f->iir->na) {
+    switch (f->iir.plan->na) {
         case 0: return launch_iir_na<0>(f, d_in, d_out, n, st);
         case 1: return launch_iir_na<1>(f, d_in, d_out, n, st);
         case 2: return launch_iir_na<2>(f, d_in, d_out, n, st);
@@ -5941,21 +5921,66 @@ static int launch_iir(fsdr_filter* f, const float* d_in, float* d_out,
     return FSDR_ERR_INVALID;
 }
 
+static int run_iir(fsdr_filter* f, const void* d_in, size_t n_in,
+                   void* d_out, size_t n_out, void* stream,
+                   fsdr_filter_result* r) {
+    hipStream_t st = (hipStream_t)stream;
+    if (d_in && d_in == d_out) {
+        set_err("iir: in-place call (d_out == d_in)");
+        return FSDR_ERR_INVALID;
+    }
+    const size_t filled = f->iir.filled;
+    size_t filled_after;
+    int status;
+    fsdr_iir_count((size_t)f->iir.plan->na, f->iir.n_b, filled, n_in,
+                   n_out, &filled_after, &r->consumed, &r->produced,
+                   &status);
+    r->status = (fsdr_status)status;
+    if (filled_after > filled) {
+        /* iir.rs:116: memory.push(i[memory.len()]) */
+        float* mem = f->iir.mem.live<float>(IIR_NA_MAX);
+        HIP_TRY(hipMemcpyAsync(mem + filled,
+                               (const float*)d_in + filled,
+                               (filled_after - filled) * sizeof(float),
+                               hipMemcpyDeviceToDevice, st));
+        f->iir.filled = filled_after;
+    }
+    if (r->produced == 0) return FSDR_OK;
+    return launch_iir(f, (const float*)d_in, (float*)d_out,
+                      (long long)r->produced, st);
+}
+
+/* `last` <- d_in[consumed-1], ordered after the kernel that read it */
 static int update_demod_last(fsdr_filter* f, const void* d_in,
                              size_t consumed, hipStream_t st) {
     if (consumed == 0) return FSDR_OK;
-    HIP_TRY(hipMemcpyAsync(f->d_hist,
+    HIP_TRY(hipMemcpyAsync(f->demod.last.ptr,
                            (const float2*)d_in + (consumed - 1),
                            sizeof(float2), hipMemcpyDeviceToDevice, st));
     return FSDR_OK;
+}
+
+static int run_quad_demod(fsdr_filter* f, const void* d_in, size_t n_in,
+                          void* d_out, size_t n_out, void* stream,
+                          fsdr_filter_result* r) {
+    hipStream_t st = (hipStream_t)stream;
+    size_t m = n_in < n_out ? n_in : n_out; /* apply.rs:108 */
+    r->consumed = r->produced = m;
+    r->status = FSDR_BOTH_SUFFICIENT;
+    if (m == 0) return FSDR_OK;
+    hipLaunchKernelGGL(k_quad_demod,
+                       dim3(grid_for((long long)m, 256)), dim3(256),
+                       0, st, (const float2*)d_in, (float*)d_out,
+                       f->demod.last.as<const float2>(), (long long)m);
+    HIP_TRY(hipGetLastError());
+    return update_demod_last(f, d_in, m, st);
 }
 
 extern "C" int fsdr_fm_demod_resamp_fused(const fsdr_filter* f) {
     if (!f || f->kind != K_FM_DEMOD_RESAMP) return 0;
     int span;
     size_t lds;
-    const char* e = getenv("FSDR_FM_FUSED");
-    return resamp_f32_tile(f, &span, &lds) && (!e || atoi(e) != 0);
+    return resamp_f32_tile(f, &span, &lds) && env_on("FSDR_FM_FUSED");
 }
 
 static int launch_fm_demod_resamp(fsdr_filter* f, const void* d_in,
@@ -5963,7 +5988,7 @@ static int launch_fm_demod_resamp(fsdr_filter* f, const void* d_in,
                                   const fsdr_filter_result* r,
                                   hipStream_t st) {
     if (r->produced) {
-        const float2* last = (const float2*)f->d_hist;
+        const float2* last = f->demod.last.as<const float2>();
         if (fsdr_fm_demod_resamp_fused(f)) {
             int span = 0;
             size_t lds = 0;
@@ -5971,30 +5996,29 @@ static int launch_fm_demod_resamp(fsdr_filter* f, const void* d_in,
             long long tiles =
                 ((long long)r->produced + RS_TILE - 1) / RS_TILE;
             int grid = (int)std::min<long long>(tiles, grid_cap(256 * 64));
-            auto kern = f->decim % 2 ? k_fm_demod_resamp<false>
+            auto kern = f->fir.decim % 2 ? k_fm_demod_resamp<false>
                                      : k_fm_demod_resamp<true>;
             hipLaunchKernelGGL(kern, dim3(grid),
                                dim3(RS_BLOCK), lds, st, (const float2*)d_in,
-                               (float*)d_out, f->d_taps, last,
-                               (int)f->n_taps, (int)f->interp,
-                               (int)f->decim, (long long)r->produced,
+                               (float*)d_out, f->fir.taps.as<float>(), last,
+                               (int)f->fir.n_taps, (int)f->fir.interp,
+                               (int)f->fir.decim, (long long)r->produced,
                                (long long)n_in, span);
             HIP_TRY(hipGetLastError());
         } else {
             /* staged: demodulate what the dot products read, then the
              * f32 resampler kernels on it */
-            const size_t tpp = f->n_taps / f->interp;
+            const size_t tpp = f->fir.n_taps / f->fir.interp;
             const size_t need =
-                (r->produced - 1) * f->decim / f->interp + tpp;
-            int rc = ensure_dev(&f->d_scratch, &f->d_scratch_bytes,
-                                need * sizeof(float));
-            if (rc) return rc;
+                (r->produced - 1) * f->fir.decim / f->fir.interp + tpp;
+            HIP_TRY(f->demod.staged.ensure(need * sizeof(float)));
             hipLaunchKernelGGL(k_quad_demod,
                                dim3(grid_for((long long)need, 256)),
                                dim3(256), 0, st, (const float2*)d_in,
-                               (float*)f->d_scratch, last, (long long)need);
+                               f->demod.staged.as<float>(), last,
+                               (long long)need);
             HIP_TRY(hipGetLastError());
-            rc = launch_resamp_f32(f, (const float*)f->d_scratch,
+            int rc = launch_resamp_f32(f, f->demod.staged.as<const float>(),
                                    (float*)d_out, r->produced, need, st);
             if (rc) return rc;
         }
@@ -6002,145 +6026,234 @@ static int launch_fm_demod_resamp(fsdr_filter* f, const void* d_in,
     return update_demod_last(f, d_in, r->consumed, st);
 }
 
+static int run_fm_demod_resamp(fsdr_filter* f, const void* d_in, size_t n_in,
+                               void* d_out, size_t n_out, void* stream,
+                               fsdr_filter_result* r) {
+    hipStream_t st = (hipStream_t)stream;
+    /* the demodulated stream is as long as the input, so the resampler's
+     * accounting applies to the Complex32 counts */
+    *r = resamp_status(f->fir.interp, f->fir.decim, f->fir.n_taps, n_in,
+                       n_out);
+    return launch_fm_demod_resamp(f, d_in, n_in, d_out, r, st);
+}
+
+static int run_fir_f32(fsdr_filter* f, const void* d_in, size_t n_in,
+                       void* d_out, size_t n_out, void* stream,
+                       fsdr_filter_result* r) {
+    hipStream_t st = (hipStream_t)stream;
+    *r = fir_status(n_in, f->fir.n_taps, n_out);
+    if (r->produced == 0) return FSDR_OK;
+    unsigned elems = 1024 + f->fir.n_padded - 1;
+    size_t lds = (size_t)elems * sizeof(float);
+    long long tiles = ((long long)r->produced + 1023) / 1024;
+    int grid = (int)std::min<long long>(tiles, grid_cap(256 * 16));
+    hipLaunchKernelGGL(k_fir_f32, dim3(grid), dim3(256), lds, st,
+                       (const float*)d_in, (float*)d_out,
+                       f->fir.taps.as<float>(), f->fir.n_padded,
+                       (long long)r->produced, (long long)n_in);
+    HIP_TRY(hipGetLastError());
+    return FSDR_OK;
+}
+
+static int run_resamp_cf32(fsdr_filter* f, const void* d_in, size_t n_in,
+                           void* d_out, size_t n_out, void* stream,
+                           fsdr_filter_result* r) {
+    hipStream_t st = (hipStream_t)stream;
+    *r = resamp_status(f->fir.interp, f->fir.decim, f->fir.n_taps, n_in,
+                       n_out);
+    if (r->produced == 0) return FSDR_OK;
+    if (f->fir.decim4 && f->fir.decim4->fir.kk_mfma &&
+        env_on("FSDR_DECIM_MFMA")) {
+        /* 1:4 shape on the MFMA decim kernel: shift the window origin back
+         * by D-1 (that kernel never reads rel < 3, so the rebased pointer
+         * stays in bounds) */
+        return launch_decim_cf32(f->fir.decim4, (const float2*)d_in - 3,
+                                 d_out, r->produced, n_in + 3, st);
+    }
+    size_t tpp = f->fir.n_taps / f->fir.interp;
+    long long span = (long long)(RS_TILE - 1) * f->fir.decim /
+                         f->fir.interp + tpp + 2;
+    size_t lds_t = (2 * (size_t)plane_floats((unsigned)span) +
+                    f->fir.n_taps) * sizeof(float);
+    if (lds_t <= 64 * 1024 && env_on("FSDR_RESAMP_TILED")) {
+        long long tiles = ((long long)r->produced + RS_TILE - 1) / RS_TILE;
+        int grid = (int)std::min<long long>(tiles, grid_cap(256 * 64));
+        hipLaunchKernelGGL(k_resamp_tiled_cf32, dim3(grid), dim3(RS_BLOCK),
+                           lds_t, st, (const float2*)d_in, (float2*)d_out,
+                           f->fir.taps.as<float>(), (int)f->fir.n_taps,
+                           (int)f->fir.interp, (int)f->fir.decim,
+                           (long long)r->produced, (long long)n_in, (int)span);
+        HIP_TRY(hipGetLastError());
+        return FSDR_OK;
+    }
+    size_t lds = f->fir.n_taps * sizeof(float);
+    hipLaunchKernelGGL(k_resamp_cf32,
+                       dim3(grid_for((long long)r->produced, 256)),
+                       dim3(256), lds, st, (const float2*)d_in,
+                       (float2*)d_out, f->fir.taps.as<float>(),
+                       (int)f->fir.n_taps, (int)f->fir.interp,
+                       (int)f->fir.decim, (long long)r->produced,
+                       (long long)n_in);
+    HIP_TRY(hipGetLastError());
+    return FSDR_OK;
+}
+
+static int run_fir_ccf32(fsdr_filter* f, const void* d_in, size_t n_in,
+                         void* d_out, size_t n_out, void* stream,
+                         fsdr_filter_result* r) {
+    hipStream_t st = (hipStream_t)stream;
+    *r = fir_status(n_in, f->fir.n_taps, n_out);
+    if (r->produced == 0) return FSDR_OK;
+    unsigned elems = 1024 + f->fir.n_taps - 1;
+    size_t lds = ((size_t)elems + f->fir.n_taps) * sizeof(float2);
+    long long tiles = ((long long)r->produced + 1023) / 1024;
+    int grid = (int)std::min<long long>(tiles, grid_cap(256 * 64));
+    hipLaunchKernelGGL(k_fir_ccf32, dim3(grid), dim3(256), lds, st,
+                       (const float2*)d_in, (float2*)d_out,
+                       f->fir.taps.as<const float2>(), (int)f->fir.n_taps,
+                       (long long)r->produced, (long long)n_in);
+    HIP_TRY(hipGetLastError());
+    return FSDR_OK;
+}
+
+static int run_xlating(fsdr_filter* f, const void* d_in, size_t n_in,
+                       void* d_out, size_t n_out, void* stream,
+                       fsdr_filter_result* r) {
+    hipStream_t st = (hipStream_t)stream;
+    *r = decim_status(f->fir.decim, n_in, f->fir.n_taps, n_out);
+    if (r->produced == 0) return FSDR_OK;
+    long long span = (long long)(XT_TILE - 1) * f->fir.decim +
+                     f->fir.n_taps + 2;
+    size_t lds_t = (2 * (size_t)plane_floats((unsigned)span) +
+                    2 * f->fir.n_taps) * sizeof(float);
+    if (lds_t <= 64 * 1024 && env_on("FSDR_XLATING_TILED")) {
+        long long tiles = ((long long)r->produced + XT_TILE - 1) / XT_TILE;
+        int grid = (int)std::min<long long>(tiles, grid_cap(256 * 64));
+        hipLaunchKernelGGL(k_xlating_decim_tiled_ccf32, dim3(grid),
+                           dim3(XT_BLOCK), lds_t, st, (const float2*)d_in,
+                           (float2*)d_out, f->fir.taps.as<const float2>(),
+                           (int)f->fir.n_taps, (int)f->fir.decim,
+                           (long long)r->produced, (long long)n_in,
+                           (double)f->xlat.theta, f->xlat.rot_re,
+                           f->xlat.rot_im, (int)span);
+        HIP_TRY(hipGetLastError());
+    } else {
+        size_t lds = f->fir.n_taps * sizeof(float2);
+        hipLaunchKernelGGL(
+            k_xlating_decim_ccf32, dim3(grid_for((long long)r->produced, 256)),
+            dim3(256), lds, st, (const float2*)d_in, (float2*)d_out,
+            f->fir.taps.as<const float2>(), (int)f->fir.n_taps,
+            (long long)f->fir.decim, (long long)r->produced, (long long)n_in,
+            f->xlat.theta, f->xlat.rot_re, f->xlat.rot_im);
+        HIP_TRY(hipGetLastError());
+    }
+    { /* advance the rotator phase (closed form, f64) */
+        double a = (double)f->xlat.theta * (double)r->produced;
+        double cs = cos(a), sn = sin(a);
+        float nr = (float)(cs * f->xlat.rot_re - sn * f->xlat.rot_im);
+        float ni = (float)(cs * f->xlat.rot_im + sn * f->xlat.rot_re);
+        f->xlat.rot_re = nr;
+        f->xlat.rot_im = ni;
+    }
+    return FSDR_OK;
+}
+
+static int run_movavg(fsdr_filter* f, const void* d_in, size_t n_in,
+                      void* d_out, size_t n_out, void* stream,
+                      fsdr_filter_result* r) {
+    hipStream_t st = (hipStream_t)stream;
+    auto& ma = f->movavg;
+    /* the work() counting loop (consume a frame, emit every history-th one,
+     * stop when input or output room runs out) in closed form: the loop
+     * itself cost ~0.15 ms of host time per call at the bench's 262143
+     * frames */
+    size_t in_frames = n_in / ma.width;
+    size_t out_frames = n_out / ma.width;
+    size_t cons = 0, prod = 0, i = ma.i;
+    movavg_count(in_frames, out_frames, ma.history, &cons, &prod, &i);
+    r->consumed = cons * ma.width;
+    r->produced = prod * ma.width;
+    r->status = FSDR_BOTH_SUFFICIENT;
+    if (cons == 0) return FSDR_OK;
+    if (prod <= 1 && (prod == 0 || ma.i + cons == ma.history)) {
+        /* parallel fast path: chunked EMA + exact composition */
+        /* FSDR_MOVAVG_SKIP=0 computes every chunk */
+        int cf, nch;
+        const int c0 =
+            movavg_plan(cons, ma.decay, env_on("FSDR_MOVAVG_SKIP"), &cf, &nch);
+        HIP_TRY(ma.partials.ensure((size_t)nch * ma.width * 4));
+        const long long live = (long long)(nch - c0) *
+                               ((ma.width & 3) == 0 ? ma.width / 4 : ma.width);
+        hipLaunchKernelGGL(k_moving_avg_chunks, dim3(grid_for(live, 256)),
+                           dim3(256), 0, st, (const float*)d_in,
+                           ma.partials.as<float>(), (int)ma.width,
+                           (long long)cons, nch, cf, ma.decay, c0);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_moving_avg_combine,
+                           dim3((unsigned)ma.width), dim3(256), 0, st,
+                           ma.partials.as<const float>(), ma.avg.as<float>(),
+                           prod ? (float*)d_out : nullptr, (int)ma.width,
+                           (long long)cons, nch, cf, ma.decay, c0);
+        HIP_TRY(hipGetLastError());
+        ma.i = i;
+        return FSDR_OK;
+    }
+    hipLaunchKernelGGL(k_moving_avg, dim3((unsigned)((ma.width + 255) / 256)),
+                       dim3(256), 0, st, (const float*)d_in, (float*)d_out,
+                       ma.avg.as<float>(), (int)ma.width, (long long)cons,
+                       (int)ma.i, (int)ma.history, ma.decay);
+    HIP_TRY(hipGetLastError());
+    ma.i = i;
+    return FSDR_OK;
+}
+
+/* one channel only (fsdr_filter_dev turns the others away) */
+static int run_pfb_arb(fsdr_filter* f, const void* d_in, size_t n_in,
+                       void* d_out, size_t n_out, void* stream,
+                       fsdr_filter_result* r) {
+    /* stateful block: stream semantics, like MovingAvg */
+    r->status = FSDR_BOTH_SUFFICIENT;
+    return fsdr_pfb_arb_resampler_stream_dev(f, d_in, n_in, n_in, d_out, n_out,
+                                             n_out, stream, &r->consumed,
+                                             &r->produced);
+}
+
+static int run_mag2(fsdr_filter* f, const void* d_in, size_t n_in,
+                    void* d_out, size_t n_out, void* stream,
+                    fsdr_filter_result* r) {
+    hipStream_t st = (hipStream_t)stream;
+    size_t m = n_in < n_out ? n_in : n_out; /* apply.rs:108 */
+    r->consumed = r->produced = m;
+    r->status = FSDR_BOTH_SUFFICIENT;
+    if (m == 0) return FSDR_OK;
+    hipLaunchKernelGGL(k_mag2, dim3(grid_for((long long)m, 256)), dim3(256), 0,
+                       st, (const float2*)d_in, (float*)d_out, (long long)m);
+    HIP_TRY(hipGetLastError());
+    return FSDR_OK;
+}
+
 extern "C" int fsdr_filter_dev(fsdr_filter* f, const void* d_in, size_t n_in,
                                void* d_out, size_t n_out, void* stream,
                                fsdr_filter_result* r) {
     REQUIRE_GPU();
     if (!f || !r) { set_err("null argument"); return FSDR_ERR_INVALID; }
-    hipStream_t st = (hipStream_t)stream;
+    int (*run)(fsdr_filter*, const void*, size_t, void*, size_t, void*,
+               fsdr_filter_result*) = nullptr;
     switch (f->kind) {
-        case K_FIR_CF32: {
-            *r = fir_status(n_in, f->n_taps, n_out);
-            return launch_fir_cf32(f, d_in, d_out, r->produced, n_in, st);
-        }
-        case K_FIR_F32: {
-            *r = fir_status(n_in, f->n_taps, n_out);
-            if (r->produced == 0) return FSDR_OK;
-            unsigned elems = 1024 + f->n_taps_padded - 1;
-            size_t lds = (size_t)elems * sizeof(float);
-            long long tiles = ((long long)r->produced + 1023) / 1024;
-            int grid = (int)std::min<long long>(tiles, grid_cap(256 * 16));
-            hipLaunchKernelGGL(k_fir_f32, dim3(grid), dim3(256), lds, st,
-                               (const float*)d_in, (float*)d_out, f->d_taps,
-                               f->n_taps_padded, (long long)r->produced,
-                               (long long)n_in);
-            HIP_TRY(hipGetLastError());
-            return FSDR_OK;
-        }
-        case K_DECIM_CF32: {
-            *r = decim_status(f->decim, n_in, f->n_taps, n_out);
-            return launch_decim_cf32(f, d_in, d_out, r->produced, n_in, st);
-        }
-        case K_RESAMP_CF32: {
-            *r = resamp_status(f->interp, f->decim, f->n_taps, n_in, n_out);
-            if (r->produced == 0) return FSDR_OK;
-            const char* dmf = getenv("FSDR_DECIM_MFMA");
-            if (f->sub && f->sub->kk_mfma && (!dmf || atoi(dmf) != 0)) {
-                /* 1:4 shape on the MFMA decim kernel: shift the window
-                 * origin back by D-1 (that kernel never reads rel < 3,
-                 * so the rebased pointer stays in bounds) */
-                return launch_decim_cf32(f->sub,
-                                         (const float2*)d_in - 3, d_out,
-                                         r->produced, n_in + 3, st);
-            }
-            size_t tpp = f->n_taps / f->interp;
-            long long span = (long long)(RS_TILE - 1) * f->decim /
-                                 f->interp + tpp + 2;
-            size_t lds_t = (2 * (size_t)plane_floats((unsigned)span) +
-                            f->n_taps) * sizeof(float);
-            const char* rt = getenv("FSDR_RESAMP_TILED");
-            if (lds_t <= 64 * 1024 && (!rt || atoi(rt) != 0)) {
-                long long tiles =
-                    ((long long)r->produced + RS_TILE - 1) / RS_TILE;
-                int grid =
-                    (int)std::min<long long>(tiles, grid_cap(256 * 64));
-                hipLaunchKernelGGL(k_resamp_tiled_cf32, dim3(grid),
-                                   dim3(RS_BLOCK), lds_t, st,
-                                   (const float2*)d_in, (float2*)d_out,
-                                   f->d_taps, (int)f->n_taps,
-                                   (int)f->interp, (int)f->decim,
-                                   (long long)r->produced, (long long)n_in,
-                                   (int)span);
-                HIP_TRY(hipGetLastError());
-                return FSDR_OK;
-            }
-            size_t lds = f->n_taps * sizeof(float);
-            hipLaunchKernelGGL(k_resamp_cf32,
-                               dim3(grid_for((long long)r->produced, 256)),
-                               dim3(256), lds, st, (const float2*)d_in,
-                               (float2*)d_out, f->d_taps, (int)f->n_taps,
-                               (int)f->interp, (int)f->decim,
-                               (long long)r->produced, (long long)n_in);
-            HIP_TRY(hipGetLastError());
-            return FSDR_OK;
-        }
-        case K_FFT_CF32: {
-            /* fft.rs:169-171 */
-            size_t m = n_in < n_out ? n_in : n_out;
-            m = (m / f->fft_len) * f->fft_len;
-            size_t cap = f->fft_len * 32;
-            if (m > cap) m = cap;
-            r->consumed = r->produced = m;
-            r->status = FSDR_BOTH_SUFFICIENT;
-            return launch_fft(f, d_in, d_out, m / f->fft_len, st);
-        }
-        case K_FIR_CCF32: {
-            *r = fir_status(n_in, f->n_taps, n_out);
-            if (r->produced == 0) return FSDR_OK;
-            unsigned elems = 1024 + f->n_taps - 1;
-            size_t lds = ((size_t)elems + f->n_taps) * sizeof(float2);
-            long long tiles = ((long long)r->produced + 1023) / 1024;
-            int grid = (int)std::min<long long>(tiles, grid_cap(256 * 64));
-            hipLaunchKernelGGL(k_fir_ccf32, dim3(grid), dim3(256), lds, st,
-                               (const float2*)d_in, (float2*)d_out,
-                               (const float2*)f->d_taps, (int)f->n_taps,
-                               (long long)r->produced, (long long)n_in);
-            HIP_TRY(hipGetLastError());
-            return FSDR_OK;
-        }
-        case K_XLATING: {
-            *r = decim_status(f->decim, n_in, f->n_taps, n_out);
-            if (r->produced == 0) return FSDR_OK;
-            long long span = (long long)(XT_TILE - 1) * f->decim +
-                             f->n_taps + 2;
-            size_t lds_t = (2 * (size_t)plane_floats((unsigned)span) +
-                            2 * f->n_taps) * sizeof(float);
-            const char* xt = getenv("FSDR_XLATING_TILED");
-            if (lds_t <= 64 * 1024 && (!xt || atoi(xt) != 0)) {
-                long long tiles =
-                    ((long long)r->produced + XT_TILE - 1) / XT_TILE;
-                int grid =
-                    (int)std::min<long long>(tiles, grid_cap(256 * 64));
-                hipLaunchKernelGGL(k_xlating_decim_tiled_ccf32,
-                                   dim3(grid), dim3(XT_BLOCK), lds_t, st,
-                                   (const float2*)d_in, (float2*)d_out,
-                                   (const float2*)f->d_taps,
-                                   (int)f->n_taps, (int)f->decim,
-                                   (long long)r->produced, (long long)n_in,
-                                   (double)f->theta, f->rot_re, f->rot_im,
-                                   (int)span);
-                HIP_TRY(hipGetLastError());
-            } else {
-                size_t lds = f->n_taps * sizeof(float2);
-                hipLaunchKernelGGL(
-                    k_xlating_decim_ccf32,
-                    dim3(grid_for((long long)r->produced, 256)), dim3(256),
-                    lds, st, (const float2*)d_in, (float2*)d_out,
-                    (const float2*)f->d_taps, (int)f->n_taps,
-                    (long long)f->decim, (long long)r->produced,
-                    (long long)n_in, f->theta, f->rot_re, f->rot_im);
-                HIP_TRY(hipGetLastError());
-            }
-            { /* advance the rotator phase (closed form, f64) */
-                double a = (double)f->theta * (double)r->produced;
-                double cs = cos(a), sn = sin(a);
-                float nr = (float)(cs * f->rot_re - sn * f->rot_im);
-                float ni = (float)(cs * f->rot_im + sn * f->rot_re);
-                f->rot_re = nr;
-                f->rot_im = ni;
-            }
-            return FSDR_OK;
-        }
+        case K_FIR_CF32: run = run_fir_cf32; break;
+        case K_FIR_F32: run = run_fir_f32; break;
+        case K_DECIM_CF32: run = run_decim_cf32; break;
+        case K_RESAMP_CF32: run = run_resamp_cf32; break;
+        case K_FFT_CF32: run = run_fft; break;
+        case K_FIR_CCF32: run = run_fir_ccf32; break;
+        case K_XLATING: run = run_xlating; break;
+        case K_MOVAVG: run = run_movavg; break;
+        case K_RESAMP_F32: run = run_resamp_f32; break;
+        case K_QUAD_DEMOD: run = run_quad_demod; break;
+        case K_FM_DEMOD_RESAMP: run = run_fm_demod_resamp; break;
+        case K_IIR_F32: run = run_iir; break;
+        case K_LORA_DEMOD: run = run_lora; break;
+        case K_MAG2: run = run_mag2; break;
         case K_PFB:
             set_err("pfb channelizer uses fsdr_pfb_channelizer_run_dev "
                     "(multi-output block)");
@@ -6149,139 +6262,20 @@ extern "C" int fsdr_filter_dev(fsdr_filter* f, const void* d_in, size_t n_in,
             set_err("pfb synthesizer uses fsdr_pfb_synthesizer_run_dev "
                     "(multi-input block)");
             return FSDR_ERR_INVALID;
-        case K_PFB_ARB: {
-            if (f->width != 1) {
+        case K_PFB_ARB:
+            if (f->pfb.channels != 1) {
                 set_err("multi-channel pfb arb resampler uses "
                         "fsdr_pfb_arb_resampler_run_dev");
                 return FSDR_ERR_INVALID;
             }
-            /* stateful block: stream semantics, like MovingAvg */
-            r->status = FSDR_BOTH_SUFFICIENT;
-            return fsdr_pfb_arb_resampler_stream_dev(
-                f, d_in, n_in, n_in, d_out, n_out, n_out, stream,
-                &r->consumed, &r->produced);
-        }
-        case K_MOVAVG: {
-            /* the work() counting loop (consume a frame, emit every
-             * history-th one, stop when input or output room runs out)
-             * in closed form: the loop itself cost ~0.15 ms of host time
-             * per call at the bench's 262143 frames */
-            size_t in_frames = n_in / f->width;
-            size_t out_frames = n_out / f->width;
-            size_t cons = 0, prod = 0, i = f->i_state;
-            movavg_count(in_frames, out_frames, f->history, &cons, &prod,
-                         &i);
-            r->consumed = cons * f->width;
-            r->produced = prod * f->width;
-            r->status = FSDR_BOTH_SUFFICIENT;
-            if (cons == 0) return FSDR_OK;
-            if (prod <= 1 &&
-                (prod == 0 || f->i_state + cons == f->history)) {
-                /* parallel fast path: chunked EMA + exact composition */
-                /* FSDR_MOVAVG_SKIP=0 computes every chunk */
-                const char* sk = getenv("FSDR_MOVAVG_SKIP");
-                int cf, nch;
-                const int c0 = movavg_plan(cons, f->decay,
-                                           !sk || atoi(sk) != 0, &cf, &nch);
-                int rc = ensure_dev(&f->d_scratch, &f->d_scratch_bytes,
-                                    (size_t)nch * f->width * 4);
-                if (rc) return rc;
-                const long long live =
-                    (long long)(nch - c0) *
-                    ((f->width & 3) == 0 ? f->width / 4 : f->width);
-                hipLaunchKernelGGL(
-                    k_moving_avg_chunks, dim3(grid_for(live, 256)),
-                    dim3(256), 0, st, (const float*)d_in,
-                    (float*)f->d_scratch, (int)f->width, (long long)cons,
-                    nch, cf, f->decay, c0);
-                HIP_TRY(hipGetLastError());
-                hipLaunchKernelGGL(k_moving_avg_combine,
-                                   dim3((unsigned)f->width), dim3(256), 0,
-                                   st, (const float*)f->d_scratch, f->d_avg,
-                                   prod ? (float*)d_out : nullptr,
-                                   (int)f->width, (long long)cons, nch, cf,
-                                   f->decay, c0);
-                HIP_TRY(hipGetLastError());
-                f->i_state = i;
-                return FSDR_OK;
-            }
-            hipLaunchKernelGGL(k_moving_avg,
-                               dim3((unsigned)((f->width + 255) / 256)),
-                               dim3(256), 0, st, (const float*)d_in,
-                               (float*)d_out, f->d_avg, (int)f->width,
-                               (long long)cons, (int)f->i_state,
-                               (int)f->history, f->decay);
-            HIP_TRY(hipGetLastError());
-            f->i_state = i;
-            return FSDR_OK;
-        }
-        case K_RESAMP_F32: {
-            *r = resamp_status(f->interp, f->decim, f->n_taps, n_in, n_out);
-            return launch_resamp_f32(f, (const float*)d_in, (float*)d_out,
-                                     r->produced, n_in, st);
-        }
-        case K_QUAD_DEMOD: {
-            size_t m = n_in < n_out ? n_in : n_out; /* apply.rs:108 */
-            r->consumed = r->produced = m;
-            r->status = FSDR_BOTH_SUFFICIENT;
-            if (m == 0) return FSDR_OK;
-            hipLaunchKernelGGL(k_quad_demod,
-                               dim3(grid_for((long long)m, 256)), dim3(256),
-                               0, st, (const float2*)d_in, (float*)d_out,
-                               (const float2*)f->d_hist, (long long)m);
-            HIP_TRY(hipGetLastError());
-            return update_demod_last(f, d_in, m, st);
-        }
-        case K_FM_DEMOD_RESAMP: {
-            /* the demodulated stream is as long as the input, so the
-             * resampler's accounting applies to the Complex32 counts */
-            *r = resamp_status(f->interp, f->decim, f->n_taps, n_in, n_out);
-            return launch_fm_demod_resamp(f, d_in, n_in, d_out, r, st);
-        }
-        case K_IIR_F32: {
-            if (d_in && d_in == d_out) {
-                set_err("iir: in-place call (d_out == d_in)");
-                return FSDR_ERR_INVALID;
-            }
-            const size_t filled = f->pfb_pushes;
-            size_t filled_after;
-            int status;
-            fsdr_iir_count((size_t)f->iir->na, f->n_taps, filled, n_in,
-                           n_out, &filled_after, &r->consumed, &r->produced,
-                           &status);
-            r->status = (fsdr_status)status;
-            if (filled_after > filled) {
-                /* iir.rs:116: memory.push(i[memory.len()]) */
-                float* mem = (float*)f->d_hist + f->i_state * IIR_NA_MAX;
-                HIP_TRY(hipMemcpyAsync(mem + filled,
-                                       (const float*)d_in + filled,
-                                       (filled_after - filled) * sizeof(float),
-                                       hipMemcpyDeviceToDevice, st));
-                f->pfb_pushes = filled_after;
-            }
-            if (r->produced == 0) return FSDR_OK;
-            return launch_iir(f, (const float*)d_in, (float*)d_out,
-                              (long long)r->produced, st);
-        }
-        case K_LORA_DEMOD: {
-            /* whole symbols only: a trailing partial one stays unconsumed */
-            *r = decim_status(f->n_taps, n_in, 1, n_out);
-            return launch_lora(f, d_in, d_out, r->produced, st);
-        }
-        case K_MAG2: {
-            size_t m = n_in < n_out ? n_in : n_out; /* apply.rs:108 */
-            r->consumed = r->produced = m;
-            r->status = FSDR_BOTH_SUFFICIENT;
-            if (m == 0) return FSDR_OK;
-            hipLaunchKernelGGL(k_mag2, dim3(grid_for((long long)m, 256)),
-                               dim3(256), 0, st, (const float2*)d_in,
-                               (float*)d_out, (long long)m);
-            HIP_TRY(hipGetLastError());
-            return FSDR_OK;
-        }
+            run = run_pfb_arb;
+            break;
     }
-    set_err("unknown filter kind");
-    return FSDR_ERR_INVALID;
+    if (!run) {
+        set_err("unknown filter kind");
+        return FSDR_ERR_INVALID;
+    }
+    return run(f, d_in, n_in, d_out, n_out, stream, r);
 }
 
 extern "C" int fsdr_filter_host(fsdr_filter* f, const void* in, size_t n_in,
@@ -6289,18 +6283,17 @@ extern "C" int fsdr_filter_host(fsdr_filter* f, const void* in, size_t n_in,
                                 fsdr_filter_result* r) {
     REQUIRE_GPU();
     if (!f || !r) { set_err("null argument"); return FSDR_ERR_INVALID; }
-    int rc = ensure_dev(&f->d_in, &f->d_in_bytes, n_in * f->item_in + 64);
-    if (rc) return rc;
-    rc = ensure_dev(&f->d_out, &f->d_out_bytes, n_out * f->item_out + 64);
-    if (rc) return rc;
+    HIP_TRY(f->stage_in.ensure(n_in * f->item_in + 64));
+    HIP_TRY(f->stage_out.ensure(n_out * f->item_out + 64));
     if (n_in)
-        HIP_TRY(hipMemcpy(f->d_in, in, n_in * f->item_in,
+        HIP_TRY(hipMemcpy(f->stage_in.ptr, in, n_in * f->item_in,
                           hipMemcpyHostToDevice));
-    rc = fsdr_filter_dev(f, f->d_in, n_in, f->d_out, n_out, nullptr, r);
+    int rc = fsdr_filter_dev(f, f->stage_in.ptr, n_in, f->stage_out.ptr, n_out,
+                         nullptr, r);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     if (r->produced)
-        HIP_TRY(hipMemcpy(out, f->d_out, r->produced * f->item_out,
+        HIP_TRY(hipMemcpy(out, f->stage_out.ptr, r->produced * f->item_out,
                           hipMemcpyDeviceToHost));
     return FSDR_OK;
 }
@@ -6317,28 +6310,27 @@ extern "C" int fsdr_pfb_channelizer_run_dev(fsdr_filter* f,
         return FSDR_ERR_INVALID;
     }
     hipStream_t st = (hipStream_t)stream;
-    size_t N = f->width, tpf = f->history, D = f->decim;
+    auto& ch = f->chan;
+    size_t N = f->pfb.channels, tpf = f->pfb.tpf, D = ch.decim;
     size_t prefill = N * tpf;
     size_t steps = n_in > prefill ? (n_in - prefill) / D : 0;
     if (steps > out_cap_per_chan) steps = out_cap_per_chan;
     if (produced_per_chan) *produced_per_chan = steps;
     if (steps == 0) return FSDR_OK;
-    int rc = ensure_dev(&f->d_in, &f->d_in_bytes, steps * N * 8);
-    if (rc) return rc;
-    int rc2 = ensure_dev(&f->d_out, &f->d_out_bytes, steps * N * 8);
-    if (rc2) return rc2;
+    HIP_TRY(ch.dots.ensure(steps * N * 8));
+    HIP_TRY(ch.spectra.ensure(steps * N * 8));
     hipLaunchKernelGGL(k_pfb_dots,
                        dim3(grid_for((long long)(steps * N), 256)),
                        dim3(256), 0, st, (const float2*)d_in,
-                       (float2*)f->d_in, (const float*)f->d_taps, (int)N,
+                       ch.dots.as<float2>(), ch.taps.as<const float>(), (int)N,
                        (int)tpf, (int)D, (long long)steps,
                        (long long)prefill, (long long)0);
     HIP_TRY(hipGetLastError());
-    rc = launch_fft(f->sub, f->d_in, f->d_out, steps, st);
+    int rc = launch_fft(f->pfb.ifft, ch.dots.ptr, ch.spectra.ptr, steps, st);
     if (rc) return rc;
     hipLaunchKernelGGL(k_pfb_scatter,
                        dim3(grid_for((long long)(steps * N), 256)),
-                       dim3(256), 0, st, (const float2*)f->d_out,
+                       dim3(256), 0, st, ch.spectra.as<const float2>(),
                        (float2*)d_out, (int)N, (long long)steps,
                        (long long)out_cap_per_chan);
     HIP_TRY(hipGetLastError());
@@ -6362,9 +6354,10 @@ extern "C" int fsdr_pfb_channelizer_stream_dev(
         return FSDR_ERR_INVALID;
     }
     hipStream_t st = (hipStream_t)stream;
-    size_t N = f->width, tpf = f->history, D = f->decim;
+    auto& ch = f->chan;
+    size_t N = f->pfb.channels, tpf = f->pfb.tpf, D = ch.decim;
     size_t prefill = N * tpf, W = N * tpf;
-    size_t p = f->pfb_pushes;
+    size_t p = ch.pushes;
     size_t T = p < W ? p : W;
     size_t fill = p < prefill ? std::min(prefill - p, n) : 0;
     size_t steps = (p + n >= prefill) ? (p + n - prefill) / D -
@@ -6378,43 +6371,39 @@ extern "C" int fsdr_pfb_channelizer_stream_dev(
     if (consumed) *consumed = cons;
     if (cons == 0) return FSDR_OK;
     /* work buffer = [hist(T), chunk(cons)] */
-    int rc = ensure_dev(&f->d_scratch, &f->d_scratch_bytes,
-                        (T + cons) * 8);
-    if (rc) return rc;
+    HIP_TRY(ch.work.ensure((T + cons) * 8));
     if (T)
-        HIP_TRY(hipMemcpyAsync(f->d_scratch, f->d_hist, T * 8,
+        HIP_TRY(hipMemcpyAsync(ch.work.ptr, ch.hist.ptr, T * 8,
                                hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync((char*)f->d_scratch + T * 8, d_chunk, cons * 8,
+    HIP_TRY(hipMemcpyAsync(ch.work.as<char>() + T * 8, d_chunk, cons * 8,
                            hipMemcpyDeviceToDevice, st));
     if (steps) {
-        rc = ensure_dev(&f->d_in, &f->d_in_bytes, steps * N * 8);
-        if (rc) return rc;
-        rc = ensure_dev(&f->d_out, &f->d_out_bytes, steps * N * 8);
-        if (rc) return rc;
+        HIP_TRY(ch.dots.ensure(steps * N * 8));
+        HIP_TRY(ch.spectra.ensure(steps * N * 8));
         hipLaunchKernelGGL(k_pfb_dots,
                            dim3(grid_for((long long)(steps * N), 256)),
-                           dim3(256), 0, st, (const float2*)f->d_scratch,
-                           (float2*)f->d_in, (const float*)f->d_taps,
+                           dim3(256), 0, st, ch.work.as<const float2>(),
+                           ch.dots.as<float2>(), ch.taps.as<const float>(),
                            (int)N, (int)tpf, (int)D, (long long)steps,
                            (long long)(p + fill), (long long)(p - T));
         HIP_TRY(hipGetLastError());
-        rc = launch_fft(f->sub, f->d_in, f->d_out, steps, st);
+        int rc =
+            launch_fft(f->pfb.ifft, ch.dots.ptr, ch.spectra.ptr, steps, st);
         if (rc) return rc;
         hipLaunchKernelGGL(k_pfb_scatter,
                            dim3(grid_for((long long)(steps * N), 256)),
-                           dim3(256), 0, st, (const float2*)f->d_out,
+                           dim3(256), 0, st, ch.spectra.as<const float2>(),
                            (float2*)d_out, (int)N, (long long)steps,
                            (long long)out_cap_per_chan);
         HIP_TRY(hipGetLastError());
     }
     /* new hist = last min(W, T+cons) samples of the work buffer */
     size_t newT = std::min(W, T + cons);
-    rc = ensure_dev(&f->d_hist, &f->d_hist_bytes, W * 8);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(f->d_hist,
-                           (char*)f->d_scratch + (T + cons - newT) * 8,
+    HIP_TRY(ch.hist.ensure(W * 8));
+    HIP_TRY(hipMemcpyAsync(ch.hist.ptr,
+                           ch.work.as<char>() + (T + cons - newT) * 8,
                            newT * 8, hipMemcpyDeviceToDevice, st));
-    f->pfb_pushes = p + cons;
+    ch.pushes = p + cons;
     return FSDR_OK;
 }
 
@@ -6427,7 +6416,7 @@ static int pfb_synth_main(fsdr_filter* f, const float2* d_in,
                           size_t in_stride, size_t S, size_t fill,
                           float2* d_out, const float2* hist_old, size_t H,
                           float2* hist_new, hipStream_t st) {
-    const size_t N = f->width, tpf = f->history;
+    const size_t N = f->pfb.channels, tpf = f->pfb.tpf;
     const size_t newH = std::min(tpf - 1, H + S);
     const size_t nn = std::min(newH, S), keep = newH - nn;
     if (hist_new && keep)
@@ -6436,8 +6425,7 @@ static int pfb_synth_main(fsdr_filter* f, const float2* d_in,
     int log2n = 0;
     while (((size_t)1 << log2n) < N) log2n++;
     SynthPlan pl;
-    const char* fe = getenv("FSDR_PFB_SYNTH_FUSED");
-    if ((!fe || atoi(fe) != 0) && pfb_synth_plan(N, tpf, &pl)) {
+    if (env_on("FSDR_PFB_SYNTH_FUSED") && pfb_synth_plan(N, tpf, &pl)) {
         const long long blocks = ((long long)S + pl.R - 1) / pl.R;
         const int grid = (int)std::min<long long>(blocks, 256 * 32);
 #define SYN_FUSED_LAUNCH(NL_)                                                \
@@ -6454,9 +6442,9 @@ static int pfb_synth_main(fsdr_filter* f, const float2* d_in,
                            (long long)in_stride, (long long)S, hist_old,     \
                            (long long)H, hist_new, (long long)(S - nn),      \
                            (long long)keep, d_out, (long long)fill,          \
-                           (const float*)f->d_taps,                          \
-                           (const float2*)f->sub->d_twid, (int)N, log2n,     \
-                           (int)tpf, pl.F, pl.G, pl.FS, pl.R, pl.hp);        \
+                           f->synth.taps.as<const float>(),                  \
+                           f->pfb.ifft->fft.twid.as<const float2>(), (int)N, \
+                           log2n, (int)tpf, pl.F, pl.G, pl.FS, pl.R, pl.hp); \
     } while (0)
         switch (pl.NL) {
             case 1: SYN_FUSED_LAUNCH(1); break;
@@ -6468,11 +6456,9 @@ static int pfb_synth_main(fsdr_filter* f, const float2* d_in,
         HIP_TRY(hipGetLastError());
         return FSDR_OK;
     }
-    int rc = ensure_dev(&f->d_in, &f->d_in_bytes, S * N * 8);
-    if (rc) return rc;
-    rc = ensure_dev(&f->d_scratch, &f->d_scratch_bytes, (H + S) * N * 8);
-    if (rc) return rc;
-    float2* v = (float2*)f->d_scratch;
+    HIP_TRY(f->synth.gathered.ensure(S * N * 8));
+    HIP_TRY(f->synth.frames.ensure((H + S) * N * 8));
+    float2* v = f->synth.frames.as<float2>();
     if (H)
         HIP_TRY(hipMemcpyAsync(v, hist_old, H * N * 8,
                                hipMemcpyDeviceToDevice, st));
@@ -6480,17 +6466,18 @@ static int pfb_synth_main(fsdr_filter* f, const float2* d_in,
         (long long)((N + 31) / 32) * (long long)((S + 31) / 32);
     hipLaunchKernelGGL(k_pfb_synth_gather,
                        dim3((unsigned)std::min<long long>(tiles, 256 * 32)),
-                       dim3(SYN_BLOCK), 0, st, d_in, (float2*)f->d_in,
-                       (int)N, (long long)in_stride, (long long)S);
+                       dim3(SYN_BLOCK), 0, st, d_in,
+                       f->synth.gathered.as<float2>(), (int)N,
+                       (long long)in_stride, (long long)S);
     HIP_TRY(hipGetLastError());
-    rc = launch_fft(f->sub, f->d_in, v + H * N, S, st);
+    int rc = launch_fft(f->pfb.ifft, f->synth.gathered.ptr, v + H * N, S, st);
     if (rc) return rc;
     if (S > fill) {
         const long long runs = ((long long)(S - fill) + SYN_TT - 1) / SYN_TT;
         hipLaunchKernelGGL(k_pfb_synth_comm,
                            dim3(grid_for(runs * (long long)N, 256)),
                            dim3(256), 0, st, (const float2*)v, d_out,
-                           (const float*)f->d_taps, (int)N, (int)tpf,
+                           f->synth.taps.as<const float>(), (int)N, (int)tpf,
                            (long long)H, (long long)fill,
                            (long long)(S - fill));
         HIP_TRY(hipGetLastError());
@@ -6512,19 +6499,19 @@ static int pfb_synth_launch(fsdr_filter* f, const float2* d_in,
                             hipStream_t st) {
     int rc = pfb_synth_main(f, d_in, in_stride, S, fill, d_out, hist_old, H,
                             hist_new, st);
-    const size_t N = f->width, L = f->history;
+    const size_t N = f->pfb.channels, L = f->pfb.tpf;
     if (rc || L == 1 || p >= 2 * L - 1) return rc;
     const size_t eb = std::min(p + S, 2 * L - 1), ne = eb - p;
-    rc = ensure_dev(&f->d_in, &f->d_in_bytes, ne * N * 8);
-    if (rc) return rc;
+    HIP_TRY(f->synth.gathered.ensure(ne * N * 8));
     const long long tiles =
         (long long)((N + 31) / 32) * (long long)((ne + 31) / 32);
     hipLaunchKernelGGL(k_pfb_synth_gather,
                        dim3((unsigned)std::min<long long>(tiles, 256 * 32)),
-                       dim3(SYN_BLOCK), 0, st, d_in, (float2*)f->d_in,
-                       (int)N, (long long)in_stride, (long long)ne);
+                       dim3(SYN_BLOCK), 0, st, d_in,
+                       f->synth.gathered.as<float2>(), (int)N,
+                       (long long)in_stride, (long long)ne);
     HIP_TRY(hipGetLastError());
-    rc = launch_fft(f->sub, f->d_in, ve + p * N, ne, st);
+    rc = launch_fft(f->pfb.ifft, f->synth.gathered.ptr, ve + p * N, ne, st);
     if (rc) return rc;
     const size_t ga = std::max(p, L - 1); /* first emitting step here */
     if (ga < eb) {
@@ -6532,7 +6519,7 @@ static int pfb_synth_launch(fsdr_filter* f, const float2* d_in,
                            dim3(grid_for((long long)((eb - ga) * N), 256)),
                            dim3(256), 0, st, (const float2*)ve,
                            d_out + (ga - p - fill) * N,
-                           (const float*)f->d_taps, (int)N, (int)L,
+                           f->synth.taps.as<const float>(), (int)N, (int)L,
                            (int)(ga - (L - 1)), (int)(eb - ga));
         HIP_TRY(hipGetLastError());
     }
@@ -6557,17 +6544,17 @@ extern "C" int fsdr_pfb_synthesizer_run_dev(fsdr_filter* f,
         return FSDR_ERR_INVALID;
     }
     size_t fill, steps;
-    pfb_synth_count(f->width, f->history, 0, n_in_per_chan, out_cap, &fill,
-                    &steps);
+    pfb_synth_count(f->pfb.channels, f->pfb.tpf, 0, n_in_per_chan, out_cap,
+                    &fill, &steps);
     if (consumed_per_chan) *consumed_per_chan = fill + steps;
-    if (produced) *produced = steps * f->width;
+    if (produced) *produced = steps * f->pfb.channels;
     if (steps == 0) return FSDR_OK; /* zero state: nothing to carry */
-    int rc = ensure_dev(&f->d_out, &f->d_out_bytes,
-                        2 * f->history * f->width * 8);
-    if (rc) return rc;
+    HIP_TRY(f->synth.early_oneshot.ensure(
+        2 * f->pfb.tpf * f->pfb.channels * 8));
     return pfb_synth_launch(f, (const float2*)d_in, in_stride, fill + steps,
                             fill, (float2*)d_out, nullptr, 0, nullptr, 0,
-                            (float2*)f->d_out, (hipStream_t)stream);
+                            f->synth.early_oneshot.as<float2>(),
+                            (hipStream_t)stream);
 }
 
 /* Streaming synthesizer: carries the last tpf-1 IFFT'd frames (the
@@ -6592,7 +6579,7 @@ extern "C" int fsdr_pfb_synthesizer_stream_dev(fsdr_filter* f,
         set_err("pfb synthesizer: n_in_per_chan exceeds in_stride");
         return FSDR_ERR_INVALID;
     }
-    const size_t N = f->width, tpf = f->history, p = f->pfb_pushes;
+    const size_t N = f->pfb.channels, tpf = f->pfb.tpf, p = f->synth.steps;
     size_t fill, steps;
     pfb_synth_count(N, tpf, p, n_in_per_chan, out_cap, &fill, &steps);
     const size_t S = fill + steps;
@@ -6600,19 +6587,17 @@ extern "C" int fsdr_pfb_synthesizer_stream_dev(fsdr_filter* f,
     if (produced) *produced = steps * N;
     if (S == 0) return FSDR_OK;
     const size_t half = (tpf - 1) * N;
-    int rc = ensure_dev(&f->d_hist, &f->d_hist_bytes, 2 * half * 8 + 8);
-    if (rc) return rc;
-    rc = ensure_dev(&f->d_early, &f->d_early_bytes, 2 * tpf * N * 8);
-    if (rc) return rc;
-    float2* h_old = (float2*)f->d_hist + f->i_state * half;
-    float2* h_new = (float2*)f->d_hist + (1 - f->i_state) * half;
-    rc = pfb_synth_launch(f, (const float2*)d_in, in_stride, S, fill,
+    HIP_TRY(f->synth.hist.buf.ensure(2 * half * 8 + 8));
+    HIP_TRY(f->synth.early.ensure(2 * tpf * N * 8));
+    float2* h_old = f->synth.hist.live<float2>(half);
+    float2* h_new = f->synth.hist.next<float2>(half);
+    int rc = pfb_synth_launch(f, (const float2*)d_in, in_stride, S, fill,
                           (float2*)d_out, h_old, std::min(p, tpf - 1),
-                          tpf > 1 ? h_new : nullptr, p, (float2*)f->d_early,
-                          (hipStream_t)stream);
+                          tpf > 1 ? h_new : nullptr, p,
+                          f->synth.early.as<float2>(), (hipStream_t)stream);
     if (rc) return rc;
-    f->i_state = 1 - f->i_state;
-    f->pfb_pushes = p + S;
+    f->synth.hist.flip();
+    f->synth.steps = p + S;
     return FSDR_OK;
 }
 
@@ -6627,8 +6612,8 @@ static int pfb_arb_launch(fsdr_filter* f, const float2* d_in,
                           unsigned long long P0, size_t M, float2* d_out,
                           size_t out_stride, float2* hist, float2* hist_next,
                           hipStream_t st) {
-    const fsdr_pfb_arb_schedule* s = f->arb;
-    const int C = (int)f->width, tpf = (int)f->history;
+    const fsdr_pfb_arb_schedule* s = f->arb.sched;
+    const int C = (int)f->pfb.channels, tpf = (int)f->pfb.tpf;
     if (fill) {
         hipLaunchKernelGGL(k_pfb_arb_fill,
                            dim3(grid_for((long long)fill * C, 256)),
@@ -6641,7 +6626,7 @@ static int pfb_arb_launch(fsdr_filter* f, const float2* d_in,
     if (M) {
         ArbSt st0;
         ArbParams p;
-        p.ck = (const ArbCk*)f->d_ck;
+        p.ck = f->arb.ck.as<const ArbCk>();
         p.rho = s->rho; p.lam = s->lam; p.opc = s->opc;
         p.P0 = P0; p.cum0 = arb_seek(s, P0, &st0);
         p.delay = s->delay; p.nff = s->nff;
@@ -6657,13 +6642,13 @@ static int pfb_arb_launch(fsdr_filter* f, const float2* d_in,
                                lds, st, x, (long long)in_stride,
                                (long long)n, (const float2*)hist, d_out,
                                (long long)out_stride, (long long)M,
-                               (const float*)f->d_taps, p, nseg);
+                               f->arb.taps.as<const float>(), p, nseg);
         else
             hipLaunchKernelGGL(k_pfb_arb<false>, dim3(grid), dim3(ARB_BLOCK),
                                lds, st, x, (long long)in_stride,
                                (long long)n, (const float2*)hist, d_out,
                                (long long)out_stride, (long long)M,
-                               (const float*)f->d_taps, p, nseg);
+                               f->arb.taps.as<const float>(), p, nseg);
         HIP_TRY(hipGetLastError());
     }
     if (hist_next) {
@@ -6682,7 +6667,7 @@ static int pfb_arb_check(const fsdr_filter* f, size_t in_stride,
         set_err("not a pfb arb resampler");
         return FSDR_ERR_INVALID;
     }
-    if (f->width > 1 && (n_in > in_stride || out_cap > out_stride)) {
+    if (f->pfb.channels > 1 && (n_in > in_stride || out_cap > out_stride)) {
         set_err("pfb arb resampler: n_in_per_chan exceeds in_stride or "
                 "out_cap_per_chan exceeds out_stride");
         return FSDR_ERR_INVALID;
@@ -6699,17 +6684,17 @@ extern "C" int fsdr_pfb_arb_resampler_run_dev(
                            out_cap_per_chan);
     if (rc) return rc;
     size_t fill, n, M;
-    arb_work(f->arb, f->history, 0, n_in_per_chan, out_cap_per_chan, &fill,
-             &n, &M);
+    arb_work(f->arb.sched, f->pfb.tpf, 0, n_in_per_chan, out_cap_per_chan,
+             &fill, &n, &M);
     if (consumed_per_chan) *consumed_per_chan = fill + n;
     if (produced_per_chan) *produced_per_chan = M;
     if (M == 0) return FSDR_OK; /* zero state: nothing to carry */
-    const size_t hb = f->width * f->history * 8;
-    rc = ensure_dev(&f->d_scratch, &f->d_scratch_bytes, hb);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(f->d_scratch, 0, hb, (hipStream_t)stream));
+    const size_t hb = f->pfb.channels * f->pfb.tpf * 8;
+    dev_buf& win = f->arb.window_oneshot;
+    HIP_TRY(win.ensure(hb));
+    HIP_TRY(hipMemsetAsync(win.ptr, 0, hb, (hipStream_t)stream));
     return pfb_arb_launch(f, (const float2*)d_in, in_stride, fill, 0, n, 0, M,
-                          (float2*)d_out, out_stride, (float2*)f->d_scratch,
+                          (float2*)d_out, out_stride, win.as<float2>(),
                           nullptr, (hipStream_t)stream);
 }
 
@@ -6724,22 +6709,23 @@ extern "C" int fsdr_pfb_arb_resampler_stream_dev(
     int rc = pfb_arb_check(f, in_stride, n_in_per_chan, out_stride,
                            out_cap_per_chan);
     if (rc) return rc;
-    const size_t tpf = f->history, p = f->pfb_pushes;
+    const size_t tpf = f->pfb.tpf, p = f->arb.consumed;
     size_t fill, n, M;
-    arb_work(f->arb, tpf, p, n_in_per_chan, out_cap_per_chan, &fill, &n, &M);
+    arb_work(f->arb.sched, tpf, p, n_in_per_chan, out_cap_per_chan, &fill, &n,
+             &M);
     if (consumed_per_chan) *consumed_per_chan = fill + n;
     if (produced_per_chan) *produced_per_chan = M;
     if (fill + n == 0) return FSDR_OK;
-    const size_t half = f->width * tpf;
-    float2* h_live = (float2*)f->d_hist + f->i_state * half;
-    float2* h_next = (float2*)f->d_hist + (1 - f->i_state) * half;
+    const size_t half = f->pfb.channels * tpf;
+    float2* h_live = f->arb.window.live<float2>(half);
+    float2* h_next = f->arb.window.next<float2>(half);
     rc = pfb_arb_launch(f, (const float2*)d_in, in_stride, fill, p, n,
                         p + fill - (n ? tpf : 0), M, (float2*)d_out,
                         out_stride, h_live, n ? h_next : nullptr,
                         (hipStream_t)stream);
     if (rc) return rc;
-    if (n) f->i_state = 1 - f->i_state;
-    f->pfb_pushes = p + fill + n;
+    if (n) f->arb.window.flip();
+    f->arb.consumed = p + fill + n;
     return FSDR_OK;
 }
 
@@ -6823,20 +6809,19 @@ extern "C" int fsdr_cmul_host(const void* a, size_t n_a, const void* b,
     REQUIRE_GPU();
     size_t mm = n_a < n_b ? n_a : n_b;
     if (n_out < mm) mm = n_out;
-    void *da = nullptr, *db = nullptr, *do_ = nullptr;
-    HIP_TRY(hipMalloc(&da, (mm ? mm : 1) * 8));
-    HIP_TRY(hipMalloc(&db, (mm ? mm : 1) * 8));
-    HIP_TRY(hipMalloc(&do_, (mm ? mm : 1) * 8));
+    dev_buf da, db, do_; /* freed on every return */
+    HIP_TRY(da.ensure((mm ? mm : 1) * 8));
+    HIP_TRY(db.ensure((mm ? mm : 1) * 8));
+    HIP_TRY(do_.ensure((mm ? mm : 1) * 8));
     if (mm) {
-        HIP_TRY(hipMemcpy(da, a, mm * 8, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(db, b, mm * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(da.ptr, a, mm * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(db.ptr, b, mm * 8, hipMemcpyHostToDevice));
     }
-    int rc = fsdr_cmul_dev(da, mm, db, mm, do_, mm, nullptr, m);
+    int rc = fsdr_cmul_dev(da.ptr, mm, db.ptr, mm, do_.ptr, mm, nullptr, m);
     if (rc == FSDR_OK && mm) {
         HIP_TRY(hipStreamSynchronize(nullptr));
-        HIP_TRY(hipMemcpy(out, do_, mm * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out, do_.ptr, mm * 8, hipMemcpyDeviceToHost));
     }
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(do_);
     return rc;
 }
 
@@ -7054,10 +7039,10 @@ struct fsdr_wlan_rx {
     bool ss_above = false;
     bool ss_pending = false;
     float ss_pending_freq = 0.f;
-    /* SyncLong GPU correlator */
+    /* SyncLong GPU correlator, its input window and its output */
     fsdr_filter* corr = nullptr;
-    void* d_win = nullptr;
-    void* d_cor = nullptr;
+    dev_buf win, cor;
+    ~fsdr_wlan_rx() { delete corr; }
 };
 
 extern "C" fsdr_wlan_rx* fsdr_wlan_rx_create(void) {
@@ -7073,13 +7058,10 @@ extern "C" fsdr_wlan_rx* fsdr_wlan_rx_create(void) {
     }
     rx->corr = fsdr_fir_ccf32_create(rev, 64);
     if (!rx->corr ||
-        hipMalloc(&rx->d_win, (WLAN_SEARCH_WINDOW + 64) * sizeof(float2)) !=
+        rx->win.ensure((WLAN_SEARCH_WINDOW + 64) * sizeof(float2)) !=
             hipSuccess ||
-        hipMalloc(&rx->d_cor, WLAN_SEARCH_WINDOW * sizeof(float2)) !=
-            hipSuccess) {
+        rx->cor.ensure(WLAN_SEARCH_WINDOW * sizeof(float2)) != hipSuccess) {
         set_err("wlan rx alloc failed");
-        fsdr_filter_destroy(rx->corr);
-        if (rx->d_win) (void)hipFree(rx->d_win);
         delete rx;
         return nullptr;
     }
@@ -7087,11 +7069,7 @@ extern "C" fsdr_wlan_rx* fsdr_wlan_rx_create(void) {
 }
 
 extern "C" void fsdr_wlan_rx_destroy(fsdr_wlan_rx* rx) {
-    if (!rx) return;
-    fsdr_filter_destroy(rx->corr);
-    if (rx->d_win) (void)hipFree(rx->d_win);
-    if (rx->d_cor) (void)hipFree(rx->d_cor);
-    delete rx;
+    if (rx) delete rx;
 }
 
 /* SyncShort actor loop (sync_short.rs:92-150) over aligned spans of the
@@ -7190,20 +7168,20 @@ extern "C" size_t fsdr_wlan_sync_long_run(
         size_t T2 = (t + 1 < num_tags) ? tag_idx[t + 1] : n;
         if (T2 - T < WLAN_SEARCH_WINDOW + 128) continue; /* :143 */
         /* Correlator::sync on in[T .. T+SEARCH_WINDOW+63] (GPU) */
-        if (hipMemcpy(rx->d_win, in + T,
+        if (hipMemcpy(rx->win.ptr, in + T,
                       (WLAN_SEARCH_WINDOW + 63) * sizeof(float2),
                       hipMemcpyHostToDevice) != hipSuccess) {
             set_err("wlan h2d failed");
             break;
         }
         fsdr_filter_result r;
-        if (fsdr_filter_dev(rx->corr, rx->d_win, WLAN_SEARCH_WINDOW + 63,
-                            rx->d_cor, WLAN_SEARCH_WINDOW, nullptr,
+        if (fsdr_filter_dev(rx->corr, rx->win.ptr, WLAN_SEARCH_WINDOW + 63,
+                            rx->cor.ptr, WLAN_SEARCH_WINDOW, nullptr,
                             &r) != FSDR_OK)
             break;
         (void)hipStreamSynchronize(nullptr);
         float2 corv[WLAN_SEARCH_WINDOW];
-        if (hipMemcpy(corv, rx->d_cor,
+        if (hipMemcpy(corv, rx->cor.ptr,
                       WLAN_SEARCH_WINDOW * sizeof(float2),
                       hipMemcpyDeviceToHost) != hipSuccess)
             break;
@@ -7271,10 +7249,9 @@ struct fsdr_chain {
     fsdr_filter* fir2 = nullptr;
     fsdr_filter* fused = nullptr; /* combined-taps decimating FIR */
     fsdr_filter* fft = nullptr;
-    float2* d_y1 = nullptr;
-    float2* d_y2 = nullptr;
-    float2* d_null = nullptr; /* NullSink scratch when caller passes NULL */
-    size_t y1_cap = 0, y2_cap = 0, null_cap = 0;
+    dev_buf y1, y2;     /* unfused path: the stage outputs */
+    dev_buf null_sink;  /* NullSink scratch when the caller passes NULL */
+    ~fsdr_chain() { delete fir1; delete fir2; delete fused; delete fft; }
 };
 
 extern "C" fsdr_chain* fsdr_chain_create(const float* taps1, size_t n_taps1,
@@ -7292,8 +7269,7 @@ extern "C" fsdr_chain* fsdr_chain_create(const float* taps1, size_t n_taps1,
      * chain tests (rel l2 1e-4). Cuts chain arithmetic from
      * (T1*4 + T2) to ~(T1+T2)*1 flops per input sample and removes the
      * y1 HBM round trip (30 -> ~12 B/sample). */
-    const char* fz = getenv("FSDR_CHAIN_FUSED");
-    if (!fz || atoi(fz) != 0) {
+    if (env_on("FSDR_CHAIN_FUSED")) {
         size_t tg = n_taps1 + n_taps2 - 1;
         std::vector<double> g(tg, 0.0);
         for (size_t a = 0; a < n_taps1; a++)
@@ -7304,7 +7280,7 @@ extern "C" fsdr_chain* fsdr_chain_create(const float* taps1, size_t n_taps1,
         c->fused = fsdr_decim_fir_cf32_create(decim, gf.data(), tg);
     }
     if (!c->fir1 || !c->fir2 || !c->fft) {
-        fsdr_chain_destroy(c);
+        delete c;
         return nullptr;
     }
     return c;
@@ -7312,20 +7288,12 @@ extern "C" fsdr_chain* fsdr_chain_create(const float* taps1, size_t n_taps1,
 
 extern "C" int fsdr_chain_variant(const fsdr_chain* c, int* fused_kk_mfma) {
     if (!c) { set_err("null chain"); return FSDR_ERR_INVALID; }
-    if (fused_kk_mfma) *fused_kk_mfma = c->fused ? c->fused->kk_mfma : 0;
+    if (fused_kk_mfma) *fused_kk_mfma = c->fused ? c->fused->fir.kk_mfma : 0;
     return FSDR_OK;
 }
 
 extern "C" void fsdr_chain_destroy(fsdr_chain* c) {
-    if (!c) return;
-    fsdr_filter_destroy(c->fir1);
-    fsdr_filter_destroy(c->fir2);
-    fsdr_filter_destroy(c->fused);
-    fsdr_filter_destroy(c->fft);
-    if (c->d_y1) (void)hipFree(c->d_y1);
-    if (c->d_y2) (void)hipFree(c->d_y2);
-    if (c->d_null) (void)hipFree(c->d_null);
-    delete c;
+    if (c) delete c;
 }
 
 extern "C" int fsdr_chain_run_dev(fsdr_chain* c, const void* d_in,
@@ -7335,8 +7303,8 @@ extern "C" int fsdr_chain_run_dev(fsdr_chain* c, const void* d_in,
     REQUIRE_GPU();
     if (!c) { set_err("null chain"); return FSDR_ERR_INVALID; }
     hipStream_t st = (hipStream_t)stream;
-    const size_t nt1 = c->fir1->n_taps, nt2 = c->fir2->n_taps;
-    const size_t D = c->fir2->decim, L = c->fft->fft_len;
+    const size_t nt1 = c->fir1->fir.n_taps, nt2 = c->fir2->fir.n_taps;
+    const size_t D = c->fir2->fir.decim, L = c->fft->fft.len;
     size_t y1 = sat_sub(n_in + 1, nt1);
     size_t y2 = sat_sub(y1 + 1, nt2) / D;
     size_t frames = y2 / L;
@@ -7347,16 +7315,17 @@ extern "C" int fsdr_chain_run_dev(fsdr_chain* c, const void* d_in,
     if (produced) *produced = prod;
     if (frames == 0) return FSDR_OK;
     int rc;
-    const char* ffz = getenv("FSDR_CHAIN_FFTFUSE");
     const bool fft_fusable =
         (L == 64 || L == 128 || L == 256 || L == 512 || L == 1024);
-    if (c->fused && fft_fusable && c->fused->kk_mfma &&
-        !c->fft->inverse && !c->fft->fft_shift && c->fft->norm == 0.f &&
-        (!ffz || atoi(ffz) != 0)) {
+    if (c->fused && fft_fusable && c->fused->fir.kk_mfma &&
+        !c->fft->fft.inverse && !c->fft->fft.shift &&
+        c->fft->fft.norm == 0.f && env_on("FSDR_CHAIN_FFTFUSE")) {
         /* single kernel: fused decimating filter + in-block per-frame
          * FFT (+ optional |X|^2) — y2 never touches HBM. Tile = 1024
          * decimated outputs = 1024/L frames. */
-        const int KK = c->fused->kk_mfma;
+        const int KK = c->fused->fir.kk_mfma;
+        const float* mtaps = c->fused->fir.mtaps.as<float>();
+        const float2* twid = c->fft->fft.twid.as<float2>();
         long long tiles = ((long long)prod + MDFIR_TILE - 1) / MDFIR_TILE;
         /* ~2 tiles/block at 2^26: best measured */
         long long cap = grid_cap(8192);
@@ -7373,117 +7342,95 @@ extern "C" int fsdr_chain_run_dev(fsdr_chain* c, const void* d_in,
         float2* spec_dst = (float2*)d_out; /* null + mag-only: skip the
                                               discarded spectra write */
         if (!spec_dst && !d_mag) { /* NullSink scratch keeps work observable */
-            rc = ensure_dev((void**)&c->d_null, &c->null_cap,
-                            (prod + 8) * sizeof(float2));
-            if (rc) return rc;
-            spec_dst = c->d_null;
+            HIP_TRY(c->null_sink.ensure((prod + 8) * sizeof(float2)));
+            spec_dst = c->null_sink.as<float2>();
         }
-        const char* b512 = getenv("FSDR_CHAIN_BLOCK512");
-        if (b512 && atoi(b512) != 0 && L == 1024 && KK == 80 &&
+        if (env_int("FSDR_CHAIN_BLOCK512", 0) != 0 && L == 1024 && KK == 80 &&
             prod % 2048 == 0) {
             long long tiles2 = (long long)prod / 2048;
             int grid2 = (int)std::min<long long>(tiles2, cap);
             using G2 = ChainGeom<80, 512, 2048>;
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_decim4_fft_mfma2_tpl<80>),
                                dim3(grid2), dim3(G2::BLOCK),
-                               G2::halves_bytes, st,
-                               (const float2*)d_in, spec_dst,
-                               c->fused->d_mtaps, (long long)prod,
-                               (long long)n_in,
-                               (const float2*)c->fft->d_twid,
-                               (float*)d_mag);
+                               G2::halves_bytes, st, (const float2*)d_in,
+                               spec_dst, mtaps, (long long)prod,
+                               (long long)n_in, twid, (float*)d_mag);
             HIP_TRY(hipGetLastError());
             return FSDR_OK;
         }
-        const char* ws = getenv("FSDR_CHAIN_WS");
         /* software-pipelined FFT-in-MFMA-shadow variant: measured ~4%
          * faster than the ap kernel at fft_len 1024 (the serial FFT
          * issues inside the MFMA pipe shadow) — default for the
          * aligned 1024 case; FSDR_CHAIN_WS=0 disables. */
-        if ((!ws || atoi(ws) != 0) && L == 1024 &&
+        if (env_on("FSDR_CHAIN_WS") && L == 1024 &&
             ((uintptr_t)d_in & 15u) == 0) {
             return chain_launch([&](auto K) {
                 using G = ChainGeom<decltype(K)::value>;
                 hipLaunchKernelGGL(
                     HIP_KERNEL_NAME(k_decim4_fft_mfma_ws_tpl<G::KKD>),
                     dim3(grid), dim3(G::BLOCK), G::ws_bytes, st,
-                    (const float2*)d_in, spec_dst, c->fused->d_mtaps,
-                    (long long)prod, (long long)n_in,
-                    (const float2*)c->fft->d_twid, (float*)d_mag);
+                    (const float2*)d_in, spec_dst, mtaps, (long long)prod,
+                    (long long)n_in, twid, (float*)d_mag);
             });
         }
-        const char* ap = getenv("FSDR_CHAIN_ALLPHASE");
         /* all-phase + aligned-group staging is the default (measured
          * ~2% faster: fewer barriers and half the staging-load
          * instructions; see profiles/pmc_sq_r02.txt). The ap kernel's
          * group staging needs a 16B-aligned input base — ring carry
          * offsets can be 8B-odd — so unaligned inputs (and
          * FSDR_CHAIN_ALLPHASE=0) take the 2-phase-halves kernel. */
-        if ((!ap || atoi(ap) != 0) && ((uintptr_t)d_in & 15u) == 0) {
+        if (env_on("FSDR_CHAIN_ALLPHASE") && ((uintptr_t)d_in & 15u) == 0) {
             return chain_launch([&](auto K) {
                 using G = ChainGeom<decltype(K)::value>;
                 hipLaunchKernelGGL(
                     HIP_KERNEL_NAME(k_decim4_fft_mfma_ap_tpl<G::KKD>),
                     dim3(grid), dim3(G::BLOCK), G::ap_bytes, st,
-                    (const float2*)d_in, spec_dst, c->fused->d_mtaps,
-                    (long long)prod, (long long)n_in,
-                    (const float2*)c->fft->d_twid, (float*)d_mag, (int)L);
+                    (const float2*)d_in, spec_dst, mtaps, (long long)prod,
+                    (long long)n_in, twid, (float*)d_mag, (int)L);
             });
         }
-        const char* occ8 = getenv("FSDR_CHAIN_OCC8");
-        if (occ8 && atoi(occ8) != 0 && KK == 80) {
+        if (env_int("FSDR_CHAIN_OCC8", 0) != 0 && KK == 80) {
             /* experiment: force 8 waves/SIMD occupancy (VGPR capped to
              * 64 by the compiler; some spill risk) */
             hipLaunchKernelGGL(
                 HIP_KERNEL_NAME((k_decim4_fft_mfma_tpl<80, 8>)),
                 dim3(grid), dim3(MDFIR_BLOCK), ChainGeom<80>::halves_bytes,
-                st,
-                (const float2*)d_in, spec_dst, c->fused->d_mtaps,
-                (long long)prod, (long long)n_in,
-                (const float2*)c->fft->d_twid, (float*)d_mag, (int)L, 0);
+                st, (const float2*)d_in, spec_dst, mtaps, (long long)prod,
+                (long long)n_in, twid, (float*)d_mag, (int)L, 0);
             HIP_TRY(hipGetLastError());
             return FSDR_OK;
         }
-        int stagger = 0;
-        if (const char* sg = getenv("FSDR_CHAIN_STAGGER"))
-            stagger = atoi(sg);
+        const int stagger = env_int("FSDR_CHAIN_STAGGER", 0);
         return chain_launch([&](auto K) {
             using G = ChainGeom<decltype(K)::value>;
             hipLaunchKernelGGL(
                 HIP_KERNEL_NAME(k_decim4_fft_mfma_tpl<G::KKD>), dim3(grid),
                 dim3(G::BLOCK), G::halves_bytes, st, (const float2*)d_in,
-                spec_dst, c->fused->d_mtaps, (long long)prod,
-                (long long)n_in, (const float2*)c->fft->d_twid,
+                spec_dst, mtaps, (long long)prod, (long long)n_in, twid,
                 (float*)d_mag, (int)L, stagger);
         });
     }
-    rc = ensure_dev((void**)&c->d_y2, &c->y2_cap,
-                    (prod + 8) * sizeof(float2));
-    if (rc) return rc;
+    HIP_TRY(c->y2.ensure((prod + 8) * sizeof(float2)));
     float2* out2 = (float2*)d_out;
     if (!out2) {
-        rc = ensure_dev((void**)&c->d_null, &c->null_cap,
-                        (prod + 8) * sizeof(float2));
-        if (rc) return rc;
-        out2 = c->d_null;
+        HIP_TRY(c->null_sink.ensure((prod + 8) * sizeof(float2)));
+        out2 = c->null_sink.as<float2>();
     }
     if (c->fused) {
-        rc = launch_decim_cf32(c->fused, d_in, c->d_y2, prod, n_in, st);
+        rc = launch_decim_cf32(c->fused, d_in, c->y2.ptr, prod, n_in, st);
         if (rc) return rc;
     } else {
         /* two-stage path: y1 covers the y2 window
          * (y2 needs y1[D-1 + (prod-1)*D + nt2-1]) */
         size_t y1_need = D - 1 + (prod - 1) * D + nt2;
-        rc = ensure_dev((void**)&c->d_y1, &c->y1_cap,
-                        (y1_need + 8) * sizeof(float2));
+        HIP_TRY(c->y1.ensure((y1_need + 8) * sizeof(float2)));
+        rc = launch_fir_cf32(c->fir1, d_in, c->y1.ptr, y1_need, n_in, st);
         if (rc) return rc;
-        rc = launch_fir_cf32(c->fir1, d_in, c->d_y1, y1_need, n_in, st);
-        if (rc) return rc;
-        rc = launch_decim_cf32(c->fir2, c->d_y1, c->d_y2, prod, y1_need,
+        rc = launch_decim_cf32(c->fir2, c->y1.ptr, c->y2.ptr, prod, y1_need,
                                st);
         if (rc) return rc;
     }
-    rc = launch_fft(c->fft, c->d_y2, out2, frames, st, (float*)d_mag);
+    rc = launch_fft(c->fft, c->y2.ptr, out2, frames, st, (float*)d_mag);
     return rc;
 }
 
