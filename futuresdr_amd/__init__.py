@@ -120,6 +120,24 @@ def _load():
     lib.fsdr_lora_demod_count.restype = ctypes.c_int
     lib.fsdr_lora_demod_count.argtypes = [ctypes.c_uint, sz, sz, szp, szp,
                                           ctypes.POINTER(ctypes.c_int)]
+    lib.fsdr_wlan_decoder_create.restype = vp
+    lib.fsdr_wlan_decoder_create.argtypes = []
+    lib.fsdr_wlan_decoder_destroy.restype = None
+    lib.fsdr_wlan_decoder_destroy.argtypes = [vp]
+    lib.fsdr_wlan_decode_dev.restype = ctypes.c_int
+    lib.fsdr_wlan_decode_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
+    lib.fsdr_wlan_decode_host.restype = ctypes.c_int
+    lib.fsdr_wlan_decode_host.argtypes = [vp, vp, vp, sz, vp, vp, vp]
+    lib.fsdr_wlan_frame_param.restype = ctypes.c_int
+    lib.fsdr_wlan_frame_param.argtypes = [ctypes.c_uint, sz, szp, szp, szp]
+    lib.fsdr_wlan_deinterleave_map.restype = ctypes.c_int
+    lib.fsdr_wlan_deinterleave_map.argtypes = [ctypes.c_uint, vp]
+    lib.fsdr_wlan_depuncture_map.restype = ctypes.c_int
+    lib.fsdr_wlan_depuncture_map.argtypes = [ctypes.c_uint, sz, sz, sz, vp]
+    lib.fsdr_wlan_signal_field.restype = ctypes.c_int
+    lib.fsdr_wlan_signal_field.argtypes = [vp, ctypes.POINTER(ctypes.c_int),
+                                           ctypes.POINTER(ctypes.c_uint),
+                                           szp]
     lib.fsdr_firdes_kaiser_multirate_f32.restype = sz
     lib.fsdr_firdes_kaiser_multirate_f32.argtypes = [sz, sz, sz,
                                                      ctypes.c_double, f32p,
@@ -1262,6 +1280,146 @@ class WlanRx:
         frames = [(int(f_off[i]), float(f_freq[i]))
                   for i in range(nf.value)]
         return out[:prod], frames
+
+
+class _WlanFrame(ctypes.Structure):
+    _fields_ = [
+        ("mcs", ctypes.c_uint32),
+        ("psdu_size", ctypes.c_uint32),
+        ("sym_off", ctypes.c_size_t),
+        ("out_off", ctypes.c_size_t),
+        ("dec_off", ctypes.c_size_t),
+    ]
+
+
+def wlan_frame_param(mcs, psdu_size):
+    """(n_symbols, n_data_bits, n_pad) of FrameParam::new (examples/wlan
+    src/lib.rs:324-343); mcs 0..7 = Bpsk_1_2 .. Qam64_3_4. Needs no
+    device."""
+    if mcs < 0 or psdu_size < 0:
+        raise FsdrError("wlan: mcs and psdu_size must not be negative")
+    ns, nd, npad = ctypes.c_size_t(), ctypes.c_size_t(), ctypes.c_size_t()
+    _check(_load().fsdr_wlan_frame_param(mcs, psdu_size, ctypes.byref(ns),
+                                         ctypes.byref(nd),
+                                         ctypes.byref(npad)))
+    return ns.value, nd.value, npad.value
+
+
+def wlan_deinterleave_map(mcs):
+    """m (n_cbps entries) with deinterleaved[m[k]] = rx_bits[k] inside one
+    symbol (decoder.rs:50-64), read off the kernel's index map. Needs no
+    device."""
+    if mcs < 0:
+        raise FsdrError("wlan: mcs must be in [0,7]")
+    out = np.zeros(288, np.uint16)
+    _check(_load().fsdr_wlan_deinterleave_map(mcs, _c(out)))
+    return out[:(48, 48, 96, 96, 192, 192, 288, 288)[mcs]].astype(np.int64)
+
+
+def wlan_depuncture_map(mcs, n_symbols, count, first=0):
+    """The kernel's source of depunctured values first .. first+count-1 of
+    a frame: 8*byte + bit into its index bytes, -1 for an erasure, -2 past
+    the frame (reads 0). Needs no device."""
+    if mcs < 0 or n_symbols < 0 or count < 0 or first < 0:
+        raise FsdrError("wlan: negative argument")
+    out = np.zeros(count, np.int32)
+    _check(_load().fsdr_wlan_depuncture_map(mcs, n_symbols, first, count,
+                                            _c(out)))
+    return out
+
+
+def wlan_signal_field(bits24):
+    """(mcs, psdu_size) of the 24 decoded SIGNAL bits (one per element,
+    e.g. np.unpackbits of the first three raw decoded bytes), or None as
+    the reference's decode_signal_field (frame_equalizer.rs:142-174).
+    Needs no device."""
+    bits = np.ascontiguousarray(bits24, np.uint8)
+    if bits.size != 24:
+        raise FsdrError("wlan: the SIGNAL field has 24 bits")
+    found, mcs, psdu = ctypes.c_int(), ctypes.c_uint(), ctypes.c_size_t()
+    _check(_load().fsdr_wlan_signal_field(_c(bits), ctypes.byref(found),
+                                          ctypes.byref(mcs),
+                                          ctypes.byref(psdu)))
+    return (mcs.value, psdu.value) if found.value else None
+
+
+class WlanDecoder:
+    """The bit work of the reference's WLAN Decoder block (examples/wlan
+    src/decoder.rs, viterbi_decoder.rs) for a batch of frames, one frame per
+    wavefront: index bytes -> deinterleave -> depuncture -> Viterbi ->
+    descramble -> CRC-32. Positions past a frame's own bits read as 0 (see
+    include/futuresdr_hip.h)."""
+
+    def __init__(self):
+        self._h = _load().fsdr_wlan_decoder_create()
+        if not self._h:
+            raise FsdrError("wlan decoder create failed: "
+                            + _load().fsdr_last_error().decode())
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _load().fsdr_wlan_decoder_destroy(self._h)
+            self._h = None
+
+    @staticmethod
+    def _descs(frames):
+        arr = (_WlanFrame * max(1, len(frames)))()
+        for d, f in zip(arr, frames):
+            if min(f) < 0:
+                raise FsdrError("wlan: negative frame field")
+            if f[0] > 0xFFFFFFFF or f[1] > 0xFFFFFFFF:
+                raise FsdrError("wlan: mcs must be in [0,7], psdu_size at "
+                                "most 1528")
+            d.mcs, d.psdu_size, d.sym_off, d.out_off, d.dec_off = f
+        return arr
+
+    def decode_dev(self, d_syms, frames, d_out_bytes, d_crc_ok,
+                   d_dec_bytes=None, stream=None):
+        """Device-pointer path (ints = device addresses), asynchronous on
+        `stream`. frames: (mcs, psdu_size, sym_off, out_off, dec_off)."""
+        frames = list(frames)
+        _check(_load().fsdr_wlan_decode_dev(
+            self._h, ctypes.c_void_p(d_syms), self._descs(frames),
+            len(frames), ctypes.c_void_p(d_out_bytes),
+            ctypes.c_void_p(d_dec_bytes or 0), ctypes.c_void_p(d_crc_ok),
+            ctypes.c_void_p(stream or 0)))
+
+    def decode(self, frames, raw=False):
+        """frames: a sequence of (mcs, psdu_size, uint8 constellation
+        indices, 48 per symbol). Returns per frame (out_bytes, crc_ok), with
+        raw=True (out_bytes, crc_ok, dec_bytes): out_bytes is the psdu_size+2
+        descrambled bytes (two SERVICE bytes, then the PSDU), dec_bytes the
+        ceil(n_data_bits/8) Viterbi bytes before descrambling."""
+        frames = [(int(m), int(p), np.ascontiguousarray(s, np.uint8))
+                  for m, p, s in frames]
+        descs, so, oo, do = [], 0, 0, 0
+        for m, p, s in frames:
+            if m < 0 or m > 7 or p < 0 or p > 1528:
+                raise FsdrError("wlan: mcs must be in [0,7], psdu_size at "
+                                "most 1528")
+            ns, nd, _ = wlan_frame_param(m, p)
+            if s.size != 48 * ns:
+                raise FsdrError(f"wlan: frame needs {48 * ns} indices, "
+                                f"got {s.size}")
+            descs.append((m, p, so, oo, do))
+            so, oo, do = so + s.size, oo + p + 2, do + (nd + 7) // 8
+        if not frames:
+            return []
+        syms = np.concatenate([s.reshape(-1) for _, _, s in frames])
+        out = np.zeros(oo, np.uint8)
+        dec = np.zeros(do, np.uint8) if raw else None
+        crc = np.zeros(len(frames), np.uint8)
+        _check(_load().fsdr_wlan_decode_host(
+            self._h, _c(syms), self._descs(descs), len(descs), _c(out),
+            _c(dec) if raw else None, _c(crc)))
+        res = []
+        for i, (m, p, so, oo, do) in enumerate(descs):
+            r = (out[oo:oo + p + 2].copy(), bool(crc[i]))
+            if raw:
+                nd = wlan_frame_param(m, p)[1]
+                r += (dec[do:do + (nd + 7) // 8].copy(),)
+            res.append(r)
+        return res
 
 
 def cmul_host(a, b):

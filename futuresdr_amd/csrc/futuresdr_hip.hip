@@ -13,7 +13,10 @@
  * filter as a blocked recurrence (chunks from zero state, end states
  * combined by doubling scans with constant matrix powers), and the LoRa
  * FFT demodulator (dechirp while staging, in-LDS FFT, argmax or max-log
- * LLRs reduced per symbol). No CUDA shims, no hipify output.
+ * LLRs reduced per symbol), and the WLAN frame decoder (deinterleave,
+ * depuncture, K=7 Viterbi, descramble and CRC-32 with one frame per
+ * wavefront and one trellis state per lane). No CUDA shims, no hipify
+ * output.
  *
  * Numerical semantics follow the reference cores (cited per function); the
  * status/consumed/produced math is bit-exact, the float results are
@@ -7240,6 +7243,538 @@ extern "C" size_t fsdr_wlan_sync_long_run(
     }
     if (num_frames) *num_frames = nf;
     return o;
+}
+
+/* ================= WLAN frame decoder ==================================
+ * The bit work of examples/wlan Decoder (src/decoder.rs:47-115) and
+ * ViterbiDecoder (src/viterbi_decoder.rs) for a batch of frames: one frame
+ * per wavefront, one trellis state per lane ("WLAN frame
+ * decoder"). No LDS, no block barrier: the symbols of 32 trellis steps are
+ * two wave-wide ballots held in scalar registers, the traceback ring is
+ * three VGPRs per lane read with v_readlane, and a wave that runs out of
+ * frames simply leaves. */
+
+#define WLAN_DEC_WAVES 4   /* frames (waves) per block */
+#define WLAN_MAX_PSDU 1528 /* lib.rs:43-44 */
+#define WLAN_MAX_SYM 511   /* lib.rs:45 */
+#define WLAN_SRC_ERASURE (-1)
+#define WLAN_SRC_PAST (-2)
+#define WLAN_CRC_RESIDUE 558161692u /* decoder.rs:89 */
+
+/* mcs 0..7: Bpsk_1_2, Bpsk_3_4, Qpsk_1_2, Qpsk_3_4, Qam16_1_2, Qam16_3_4,
+ * Qam64_2_3, Qam64_3_4 (lib.rs:223-282). punct: 0 rate 1/2 (no
+ * puncturing), 1 rate 2/3 (pattern 1110), 2 rate 3/4 (pattern 111001). */
+__host__ __device__ static inline unsigned wlan_n_bpsc(unsigned mcs) {
+    return mcs < 2 ? 1 : mcs < 4 ? 2 : mcs < 6 ? 4 : 6;
+}
+__host__ __device__ static inline unsigned wlan_punct(unsigned mcs) {
+    return (mcs & 1) ? 2 : mcs == 6 ? 1 : 0;
+}
+__host__ __device__ static inline unsigned wlan_n_dbps(unsigned mcs) {
+    const unsigned n_cbps = 48 * wlan_n_bpsc(mcs), p = wlan_punct(mcs);
+    return p == 0 ? n_cbps / 2 : p == 1 ? n_cbps / 3 * 2 : n_cbps / 4 * 3;
+}
+/* viterbi_decoder.rs:68-78 */
+__host__ __device__ static inline unsigned wlan_n_traceback(unsigned mcs) {
+    const unsigned p = wlan_punct(mcs);
+    return p == 0 ? 5 : p == 1 ? 9 : 10;
+}
+/* lib.rs:324-343 */
+__host__ __device__ static inline unsigned wlan_n_symbols(unsigned mcs,
+                                                          size_t psdu) {
+    const size_t bits = 16 + 8 * psdu + 6, d = wlan_n_dbps(mcs);
+    return (unsigned)((bits + d - 1) / d);
+}
+
+/* Where depunctured value p of a frame comes from: 8 * (index byte) + bit,
+ * WLAN_SRC_ERASURE for a punctured position (the reference's value 2), or
+ * WLAN_SRC_PAST beyond the frame's own bits (reads 0, the tail rule). This
+ * is decoder.rs:69-76 (bits), :47-67 (deinterleave) and viterbi_decoder.rs:
+ * 81-107 (depuncture) composed and inverted: pattern position -> coded bit
+ * c; c -> symbol and deinterleaved position d; d -> received position k by
+ * the interleaver's two permutations (the inverses of second[] and first[]);
+ * k -> byte k / n_bpsc, bit k % n_bpsc. n_coded = n_symbols * n_cbps is a
+ * multiple of the pattern's ones, so the depunctured length is whole
+ * patterns. */
+template <unsigned BPSC, unsigned PUNCT>
+__host__ __device__ static inline int wlan_src_tpl(unsigned p,
+                                                   unsigned n_coded) {
+    constexpr unsigned N = 48 * BPSC, S = BPSC >= 2 ? BPSC / 2 : 1;
+    unsigned c;
+    if (PUNCT == 0) {
+        if (p >= n_coded) return WLAN_SRC_PAST;
+        c = p;
+    } else if (PUNCT == 1) {
+        const unsigned q = p >> 2, r = p & 3;
+        if (q * 3 >= n_coded) return WLAN_SRC_PAST;
+        if (r == 3) return WLAN_SRC_ERASURE;
+        c = q * 3 + r;
+    } else {
+        const unsigned q = p / 6, r = p - q * 6;
+        if (q * 4 >= n_coded) return WLAN_SRC_PAST;
+        if (r == 3 || r == 4) return WLAN_SRC_ERASURE;
+        c = q * 4 + (r == 5 ? 3 : r);
+    }
+    const unsigned sym = c / N, d = c - sym * N;
+    const unsigned i = (N / 16) * (d & 15) + (d >> 4);
+    const unsigned k = S * (i / S) + (i + N - 16 * i / N) % S;
+    return (int)(((sym * 48 + k / BPSC) << 3) | (k % BPSC));
+}
+
+__host__ __device__ static inline int wlan_src(unsigned bpsc, unsigned punct,
+                                               unsigned p, unsigned n_coded) {
+#define WLAN_SRC_P(B_)                                                       \
+    (punct == 0   ? wlan_src_tpl<B_, 0>(p, n_coded)                          \
+     : punct == 1 ? wlan_src_tpl<B_, 1>(p, n_coded)                          \
+                  : wlan_src_tpl<B_, 2>(p, n_coded))
+    switch (bpsc) {
+        case 1: return WLAN_SRC_P(1);
+        case 2: return WLAN_SRC_P(2);
+        case 4: return WLAN_SRC_P(4);
+        default: return WLAN_SRC_P(6);
+    }
+#undef WLAN_SRC_P
+}
+
+/* byte-wise table of the reflected CRC-32 (polynomial 0xedb88320) */
+struct WlanCrcTab {
+    unsigned v[256];
+    constexpr WlanCrcTab() : v() {
+        for (unsigned i = 0; i < 256; i++) {
+            unsigned c = i;
+            for (int b = 0; b < 8; b++)
+                c = (c >> 1) ^ (0xedb88320u & (0u - (c & 1)));
+            v[i] = c;
+        }
+    }
+};
+__constant__ WlanCrcTab wlan_crc_tab = WlanCrcTab();
+
+struct WlanFrameDesc {
+    unsigned mcs, psdu, n_sym, n_bytes; /* n_bytes = ceil(n_data_bits / 8) */
+    unsigned long long sym_off, out_off, dec_off;
+};
+
+/* max over the wave, in every lane's view a scalar: four rotate-and-max
+ * steps leave each row of 16 lanes holding its maximum, the four rows are
+ * read out with v_readlane. */
+__device__ __forceinline__ int wlan_wave_max(int v) {
+    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x121, 0xf, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x122, 0xf, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x124, 0xf, 0xf, false));
+    v = max(v, __builtin_amdgcn_update_dpp(v, v, 0x128, 0xf, 0xf, false));
+    return max(max(__builtin_amdgcn_readlane(v, 0),
+                   __builtin_amdgcn_readlane(v, 16)),
+               max(__builtin_amdgcn_readlane(v, 32),
+                   __builtin_amdgcn_readlane(v, 48)));
+}
+
+/* One frame per wave; frames strided over the grid's waves.
+ *
+ * Lane L is trellis state L, which is also the reference's storage index:
+ * its new entry comes from old entries j = L >> 1 and j + 32 with
+ * branch-table index j (viterbi_decoder.rs:184-189, 240-258). Per step a
+ * lane first forms the reference's shifted path byte for its OWN old
+ * entry -- the 16-bit pair shift hands bit 7 of an even entry to bit 0 of
+ * its odd neighbour (:216-228), and the upper half adds 1 mod 256
+ * (:233-235) -- packs it with its metric, and two ds_bpermute fetch the
+ * pair for j and j + 32. The decision is the reference's strict m0 > m1.
+ *
+ * Depunctured values are numbered p' = p + 4, so that output group g (6
+ * steps for g = 0, then 8 each, :504-523) owns p' in [16 g, 16 g + 16). A
+ * chunk is 64 values, one per lane: every lane maps its p to an index
+ * byte and bit (wlan_src), loads it, and two ballots turn the chunk into
+ * a 64-bit value mask and a 64-bit erasure mask, both wave-uniform. The
+ * next chunk's bytes are loaded before the current chunk's 32 steps run.
+ *
+ * The traceback ring (ppresult, :435-484) is the last 10 path bytes of
+ * each lane in r0..r2, newest in the low byte of r0; the walk reads them
+ * with v_readlane at the wave-uniform state. Descrambling and the CRC-32
+ * run per output byte on wave-uniform values; bytes are collected one per
+ * lane and stored 64 at a time. */
+__global__ __launch_bounds__(64 * WLAN_DEC_WAVES) void k_wlan_decode(
+    const unsigned char* __restrict__ syms,
+    const WlanFrameDesc* __restrict__ frames, int n_frames,
+    unsigned char* __restrict__ out, unsigned char* __restrict__ dec,
+    unsigned char* __restrict__ crc_ok) {
+    const unsigned lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const bool odd = lane & 1, upper = lane >= 32;
+    const unsigned bt0 = __popc((lane & ~1u) & 0x6d) & 1; /* :56-60 */
+    const unsigned bt1 = __popc((lane & ~1u) & 0x4f) & 1;
+    const int addr_lo = (int)(lane >> 1) * 4, addr_hi = addr_lo + 32 * 4;
+
+    for (int f = (int)blockIdx.x * WLAN_DEC_WAVES + wave; f < n_frames;
+         f += (int)gridDim.x * WLAN_DEC_WAVES) {
+        const WlanFrameDesc fr = frames[f];
+        const unsigned bpsc = wlan_n_bpsc(fr.mcs), punct = wlan_punct(fr.mcs);
+        const unsigned T = wlan_n_traceback(fr.mcs);
+        const unsigned n_coded = fr.n_sym * 48 * bpsc;
+        const unsigned G = T + fr.n_bytes; /* get_output calls */
+        const unsigned char* s = syms + fr.sym_off;
+
+        int metric = 0;
+        unsigned path = 0, r0 = 0, r1 = 0, r2 = 0;
+        unsigned state = 0, crc = 0xffffffffu; /* wave-uniform */
+        unsigned obyte = 0, dbyte = 0;         /* this lane's pending bytes */
+
+        auto fetch = [&](unsigned ch, int& src) -> unsigned {
+            const unsigned pp = ch * 64 + lane;
+            src = pp < 4 ? WLAN_SRC_PAST
+                         : wlan_src(bpsc, punct, pp - 4, n_coded);
+            return src >= 0 ? s[src >> 3] : 0u;
+        };
+        int src;
+        unsigned byte = fetch(0, src);
+
+        for (unsigned ch = 0; ch * 4 < G; ch++) {
+            const unsigned long long vm = __ballot((byte >> (src & 7)) & 1);
+            const unsigned long long em = __ballot(src == WLAN_SRC_ERASURE);
+            byte = fetch(ch + 1, src); /* nothing is loaded past the frame */
+            const unsigned g_end = min(4u, G - ch * 4);
+            for (unsigned gg = 0; gg < g_end; gg++) {
+                const unsigned g = ch * 4 + gg;
+                const unsigned v16 = (unsigned)(vm >> (16 * gg)) & 0xffffu;
+                const unsigned e16 = (unsigned)(em >> (16 * gg)) & 0xffffu;
+#pragma unroll
+                for (int t = 0; t < 8; t++) {
+                    if (t < 2 && g == 0) continue; /* p' 0..3 do not exist */
+                    const unsigned s0 = (v16 >> (2 * t)) & 1;
+                    const unsigned s1 = (v16 >> (2 * t + 1)) & 1;
+                    const unsigned w0 = ~(e16 >> (2 * t)) & 1;
+                    const unsigned w1 = ~(e16 >> (2 * t + 1)) & 1;
+                    /* shifted path of this lane's old entry */
+                    const unsigned up = (unsigned)__builtin_amdgcn_update_dpp(
+                        0, (int)path, 0x111 /* row_shr:1 */, 0xf, 0xf, false);
+                    unsigned sh = (path << 1) | (odd ? (up >> 7) & 1 : 0u);
+                    sh = (sh + (upper ? 1u : 0u)) & 0xffu;
+                    const int pack = metric | (int)(sh << 16);
+                    const int lo = __builtin_amdgcn_ds_bpermute(addr_lo, pack);
+                    const int hi = __builtin_amdgcn_ds_bpermute(addr_hi, pack);
+                    /* branch metrics, :161-189: an erased symbol drops out */
+                    const int bm = (int)((w0 & (bt0 ^ s0)) + (w1 & (bt1 ^ s1)));
+                    const int mx = (int)(w0 + w1);
+                    const int add_lo = odd ? bm : mx - bm;
+                    const int m_lo = (lo & 0xffff) + add_lo;
+                    const int m_hi = (hi & 0xffff) + (mx - add_lo);
+                    const bool d = m_lo > m_hi; /* strict, :198-199 */
+                    metric = d ? m_lo : m_hi;
+                    path = (unsigned)(d ? lo : hi) >> 16;
+                }
+
+                /* viterbi_get_output_generic, :435-484 */
+                r2 = (r2 << 8) | (r1 >> 24);
+                r1 = (r1 << 8) | (r0 >> 24);
+                r0 = (r0 << 8) | path;
+                const int kmax = wlan_wave_max((metric << 6) | (int)(63 - lane));
+                const int mmin = -wlan_wave_max(-metric);
+                int best = 63 - (kmax & 63); /* first strict maximum */
+#pragma unroll
+                for (unsigned k = 0; k < 9; k++) {
+                    if (k < T - 1) {
+                        const unsigned w = (unsigned)__builtin_amdgcn_readlane(
+                            (int)(k < 4 ? r0 : k < 8 ? r1 : r2), best);
+                        best = (int)(((w >> (8 * (k & 3))) & 0xffu) >> 2);
+                    }
+                }
+                /* entry T-1 back: byte 0 of r1 (T 5), byte 0 or 1 of r2 */
+                const unsigned c =
+                    ((unsigned)__builtin_amdgcn_readlane((int)(T == 5 ? r1 : r2),
+                                                         best) >>
+                     (T == 10 ? 8 : 0)) & 0xffu;
+                path = 0;
+                metric -= mmin;
+
+                if (g < T) continue; /* the first T bytes are dropped */
+                const unsigned n = g - T, slot = n & 63;
+                if (lane == slot) dbyte = c;
+                if (dec && (slot == 63 || n == fr.n_bytes - 1) && lane <= slot)
+                    dec[fr.dec_off + (n - slot) + lane] = (unsigned char)dbyte;
+                if (n >= fr.psdu + 2) continue;
+
+                /* descramble, decoder.rs:92-115: decoded bit 8n+b is bit
+                 * 7-b of c; bits 0..6 are the scrambler state itself */
+                unsigned ob;
+                if (n == 0) {
+                    state = c >> 1;
+                    const unsigned fb = ((state >> 6) ^ (state >> 3)) & 1;
+                    ob = state | ((fb ^ (c & 1)) << 7);
+                    state = ((state << 1) & 0x7e) | fb;
+                } else {
+                    /* four feedback bits at a time: x6^x3, x5^x2, x4^x1,
+                     * x3^x0 of the state x read only bits the four shifts
+                     * have not replaced, and end up as its low nibble */
+                    const unsigned t0 = ((state >> 3) ^ state) & 0xf;
+                    state = ((state << 4) & 0x70) | t0;
+                    const unsigned t1 = ((state >> 3) ^ state) & 0xf;
+                    state = ((state << 4) & 0x70) | t1;
+                    ob = __brev(c ^ ((t0 << 4) | t1)) >> 24;
+                }
+                if (n >= 2) /* reflected CRC-32 over out_bytes[2..] */
+                    crc = wlan_crc_tab.v[(crc ^ ob) & 0xff] ^ (crc >> 8);
+                if (lane == slot) obyte = ob;
+                if ((slot == 63 || n == fr.psdu + 1) && lane <= slot)
+                    out[fr.out_off + (n - slot) + lane] = (unsigned char)obyte;
+            }
+        }
+        if (lane == 0) crc_ok[f] = (unsigned char)(~crc == WLAN_CRC_RESIDUE);
+    }
+}
+
+/* ---- WLAN frame decoder: host-only helpers and the handle -------------- */
+
+static bool wlan_mcs_ok(unsigned mcs) {
+    if (mcs > 7) {
+        set_err("wlan: mcs must be in [0,7]");
+        return false;
+    }
+    return true;
+}
+
+extern "C" int fsdr_wlan_frame_param(unsigned mcs, size_t psdu_size,
+                                     size_t* n_symbols, size_t* n_data_bits,
+                                     size_t* n_pad) {
+    if (!wlan_mcs_ok(mcs)) return FSDR_ERR_INVALID;
+    if (psdu_size > 4095) { /* the SIGNAL length field has 12 bits */
+        set_err("wlan: psdu_size must be at most 4095");
+        return FSDR_ERR_INVALID;
+    }
+    const size_t ns = wlan_n_symbols(mcs, psdu_size);
+    const size_t nd = ns * wlan_n_dbps(mcs);
+    if (n_symbols) *n_symbols = ns;
+    if (n_data_bits) *n_data_bits = nd;
+    if (n_pad) *n_pad = nd - (16 + 8 * psdu_size + 6);
+    return FSDR_OK;
+}
+
+extern "C" int fsdr_wlan_deinterleave_map(unsigned mcs, uint16_t* out) {
+    if (!wlan_mcs_ok(mcs) || !out) {
+        if (mcs <= 7) set_err("wlan: null argument");
+        return FSDR_ERR_INVALID;
+    }
+    /* read off the kernel's own map, without puncturing: deinterleaved
+     * position d of symbol 0 comes from received bit k */
+    const unsigned bpsc = wlan_n_bpsc(mcs), n_cbps = 48 * bpsc;
+    for (unsigned d = 0; d < n_cbps; d++) {
+        const int src = wlan_src(bpsc, 0, d, n_cbps);
+        out[(unsigned)(src >> 3) * bpsc + (unsigned)(src & 7)] = (uint16_t)d;
+    }
+    return FSDR_OK;
+}
+
+extern "C" int fsdr_wlan_depuncture_map(unsigned mcs, size_t n_symbols,
+                                        size_t first, size_t count,
+                                        int32_t* out) {
+    if (!wlan_mcs_ok(mcs)) return FSDR_ERR_INVALID;
+    if (n_symbols > WLAN_MAX_SYM || first + count > ((size_t)1 << 24) ||
+        (count && !out)) {
+        set_err("wlan: depuncture map range");
+        return FSDR_ERR_INVALID;
+    }
+    const unsigned bpsc = wlan_n_bpsc(mcs);
+    for (size_t i = 0; i < count; i++)
+        out[i] = wlan_src(bpsc, wlan_punct(mcs), (unsigned)(first + i),
+                          (unsigned)n_symbols * 48 * bpsc);
+    return FSDR_OK;
+}
+
+/* frame_equalizer.rs:142-174 */
+extern "C" int fsdr_wlan_signal_field(const uint8_t* bits24, int* found,
+                                      unsigned* mcs, size_t* psdu_size) {
+    if (!bits24 || !found) {
+        set_err("wlan: null argument");
+        return FSDR_ERR_INVALID;
+    }
+    unsigned r = 0, bytes = 0, parity = 0;
+    for (int i = 0; i < 17; i++) {
+        const unsigned b = bits24[i] > 0;
+        parity ^= b;
+        if (i < 4) r |= b << i;
+        if (i > 4) bytes |= b << (i - 5);
+    }
+    static const int rate_to_mcs[16] = {-1, -1, -1, -1, -1, -1, -1, -1,
+                                        6,  4,  2,  0,  7,  5,  3,  1};
+    *found = 0;
+    if (parity != (unsigned)(bits24[17] > 0) || rate_to_mcs[r] < 0)
+        return FSDR_OK;
+    *found = 1;
+    if (mcs) *mcs = (unsigned)rate_to_mcs[r];
+    if (psdu_size) *psdu_size = bytes;
+    return FSDR_OK;
+}
+
+struct fsdr_wlan_decoder {
+    dev_buf desc; /* the frame descriptors the kernel reads */
+    /* pinned image of them; `uploaded` fires once the copy has read it */
+    WlanFrameDesc* pinned = nullptr;
+    size_t pinned_cap = 0;
+    hipEvent_t uploaded = nullptr;
+    /* staging of fsdr_wlan_decode_host */
+    dev_buf st_syms, st_out, st_dec, st_crc;
+    ~fsdr_wlan_decoder() {
+        if (uploaded) {
+            (void)hipEventSynchronize(uploaded);
+            (void)hipEventDestroy(uploaded);
+        }
+        if (pinned) (void)hipHostFree(pinned);
+    }
+};
+
+extern "C" fsdr_wlan_decoder* fsdr_wlan_decoder_create(void) {
+    return new fsdr_wlan_decoder(); /* buffers come with the first call */
+}
+
+extern "C" void fsdr_wlan_decoder_destroy(fsdr_wlan_decoder* dec) {
+    delete dec;
+}
+
+/* Validates the batch; fills the three span lengths when asked. */
+static int wlan_check_frames(const fsdr_wlan_decoder* dec,
+                             const fsdr_wlan_frame* frames, size_t n_frames,
+                             size_t* sym_span, size_t* out_span,
+                             size_t* dec_span) {
+    if (!dec) {
+        set_err("wlan: null decoder");
+        return FSDR_ERR_INVALID;
+    }
+    if (n_frames && !frames) {
+        set_err("wlan: null frame array");
+        return FSDR_ERR_INVALID;
+    }
+    if (n_frames > (size_t)1 << 30) {
+        set_err("wlan: too many frames");
+        return FSDR_ERR_INVALID;
+    }
+    size_t ss = 0, os = 0, ds = 0;
+    for (size_t i = 0; i < n_frames; i++) {
+        const fsdr_wlan_frame& f = frames[i];
+        if (!wlan_mcs_ok(f.mcs)) return FSDR_ERR_INVALID;
+        if (f.psdu_size > WLAN_MAX_PSDU) {
+            set_err("wlan: psdu_size must be at most 1528");
+            return FSDR_ERR_INVALID;
+        }
+        const size_t ns = wlan_n_symbols(f.mcs, f.psdu_size);
+        if (ns > WLAN_MAX_SYM) {
+            set_err("wlan: frame has more than 511 symbols");
+            return FSDR_ERR_INVALID;
+        }
+        ss = std::max(ss, f.sym_off + 48 * ns);
+        os = std::max(os, f.out_off + f.psdu_size + 2);
+        ds = std::max(ds, f.dec_off + (ns * wlan_n_dbps(f.mcs) + 7) / 8);
+    }
+    if (sym_span) *sym_span = ss;
+    if (out_span) *out_span = os;
+    if (dec_span) *dec_span = ds;
+    return FSDR_OK;
+}
+
+static int wlan_launch(fsdr_wlan_decoder* dec, const void* d_syms,
+                       const fsdr_wlan_frame* frames, size_t n_frames,
+                       void* d_out, void* d_dec, void* d_crc,
+                       hipStream_t st) {
+    if (!dec->uploaded)
+        HIP_TRY(hipEventCreateWithFlags(&dec->uploaded,
+                                        hipEventDisableTiming));
+    /* the previous call's copy may still be reading the pinned image */
+    HIP_TRY(hipEventSynchronize(dec->uploaded));
+    if (dec->pinned_cap < n_frames) {
+        if (dec->pinned) HIP_TRY(hipHostFree(dec->pinned));
+        dec->pinned = nullptr;
+        dec->pinned_cap = 0;
+        HIP_TRY(hipHostMalloc((void**)&dec->pinned,
+                              n_frames * sizeof(WlanFrameDesc)));
+        dec->pinned_cap = n_frames;
+    }
+    for (size_t i = 0; i < n_frames; i++) {
+        const fsdr_wlan_frame& f = frames[i];
+        WlanFrameDesc& d = dec->pinned[i];
+        d.mcs = f.mcs;
+        d.psdu = (unsigned)f.psdu_size;
+        d.n_sym = wlan_n_symbols(f.mcs, f.psdu_size);
+        d.n_bytes = (d.n_sym * wlan_n_dbps(f.mcs) + 7) / 8;
+        d.sym_off = f.sym_off;
+        d.out_off = f.out_off;
+        d.dec_off = f.dec_off;
+    }
+    HIP_TRY(dec->desc.ensure(n_frames * sizeof(WlanFrameDesc)));
+    HIP_TRY(hipMemcpyAsync(dec->desc.ptr, dec->pinned,
+                           n_frames * sizeof(WlanFrameDesc),
+                           hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(dec->uploaded, st));
+    const long long blocks =
+        ((long long)n_frames + WLAN_DEC_WAVES - 1) / WLAN_DEC_WAVES;
+    const int grid = (int)std::min<long long>(blocks, grid_cap(256 * 8));
+    hipLaunchKernelGGL(k_wlan_decode, dim3(grid), dim3(64 * WLAN_DEC_WAVES),
+                       0, st, (const unsigned char*)d_syms,
+                       dec->desc.as<const WlanFrameDesc>(), (int)n_frames,
+                       (unsigned char*)d_out, (unsigned char*)d_dec,
+                       (unsigned char*)d_crc);
+    HIP_TRY(hipGetLastError());
+    return FSDR_OK;
+}
+
+extern "C" int fsdr_wlan_decode_dev(fsdr_wlan_decoder* dec,
+                                    const void* d_syms,
+                                    const fsdr_wlan_frame* frames,
+                                    size_t n_frames, void* d_out_bytes,
+                                    void* d_dec_bytes, void* d_crc_ok,
+                                    void* stream) {
+    int rc = wlan_check_frames(dec, frames, n_frames, nullptr, nullptr,
+                               nullptr);
+    if (rc) return rc;
+    if (n_frames == 0) return FSDR_OK;
+    if (!d_syms || !d_out_bytes || !d_crc_ok) {
+        set_err("wlan: null device pointer");
+        return FSDR_ERR_INVALID;
+    }
+    REQUIRE_GPU();
+    return wlan_launch(dec, d_syms, frames, n_frames, d_out_bytes,
+                       d_dec_bytes, d_crc_ok, (hipStream_t)stream);
+}
+
+extern "C" int fsdr_wlan_decode_host(fsdr_wlan_decoder* dec,
+                                     const uint8_t* syms,
+                                     const fsdr_wlan_frame* frames,
+                                     size_t n_frames, uint8_t* out_bytes,
+                                     uint8_t* dec_bytes, uint8_t* crc_ok) {
+    size_t ss = 0, os = 0, ds = 0;
+    int rc = wlan_check_frames(dec, frames, n_frames, &ss, &os, &ds);
+    if (rc) return rc;
+    if (n_frames == 0) return FSDR_OK;
+    if (!syms || !out_bytes || !crc_ok) {
+        set_err("wlan: null argument");
+        return FSDR_ERR_INVALID;
+    }
+    REQUIRE_GPU();
+    HIP_TRY(dec->st_syms.ensure(ss));
+    HIP_TRY(dec->st_out.ensure(os));
+    HIP_TRY(dec->st_crc.ensure(n_frames));
+    if (dec_bytes) HIP_TRY(dec->st_dec.ensure(ds));
+    HIP_TRY(hipMemcpy(dec->st_syms.ptr, syms, ss, hipMemcpyHostToDevice));
+    rc = wlan_launch(dec, dec->st_syms.ptr, frames, n_frames, dec->st_out.ptr,
+                     dec_bytes ? dec->st_dec.ptr : nullptr, dec->st_crc.ptr,
+                     nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    /* only the frames' own ranges reach the caller's spans */
+    std::vector<uint8_t> h(std::max(os, ds));
+    HIP_TRY(hipMemcpy(h.data(), dec->st_out.ptr, os, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n_frames; i++)
+        memcpy(out_bytes + frames[i].out_off, h.data() + frames[i].out_off,
+               frames[i].psdu_size + 2);
+    if (dec_bytes) {
+        HIP_TRY(hipMemcpy(h.data(), dec->st_dec.ptr, ds,
+                          hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < n_frames; i++) {
+            const fsdr_wlan_frame& f = frames[i];
+            const size_t nb = (wlan_n_symbols(f.mcs, f.psdu_size) *
+                                   (size_t)wlan_n_dbps(f.mcs) + 7) / 8;
+            memcpy(dec_bytes + f.dec_off, h.data() + f.dec_off, nb);
+        }
+    }
+    HIP_TRY(hipMemcpy(crc_ok, dec->st_crc.ptr, n_frames,
+                      hipMemcpyDeviceToHost));
+    return FSDR_OK;
 }
 
 /* ================= chain ============================================== */

@@ -524,6 +524,83 @@ size_t fsdr_wlan_sync_long_run(fsdr_wlan_rx* rx, const fsdr_cf32* in,
                                size_t* frame_off, float* frame_freq,
                                size_t frame_cap, size_t* num_frames);
 
+/* WLAN frame decoder — the bit work of examples/wlan Decoder (src/
+ * decoder.rs:47-115) and ViterbiDecoder (src/viterbi_decoder.rs) for a batch
+ * of frames in one kernel, one frame per wavefront: constellation indices
+ * -> bits (bit k < n_bpsc of index i is rx bit i*n_bpsc + k, higher bits
+ * of the byte ignored) -> per-symbol deinterleave -> depuncture (erasures
+ * where the pattern is 0) -> hard-decision K=7 Viterbi (polynomials 0x6d,
+ * 0x4f; byte paths shifted as 16-bit pairs; strict m0 > m1; get_output
+ * after 6 trellis steps and then every 8, with a ring of n_traceback = 5, 10
+ * or 9 entries for rates 1/2, 3/4, 2/3; best state = first maximum; the
+ * first n_traceback bytes dropped) -> descramble (x^7+x^4+1, state from
+ * decoded bits 0..6, out_bytes[0] = state, bits 7.. packed LSB first) ->
+ * crc_ok = (CRC-32 of out_bytes[2 .. psdu+2] == 558161692). All integer;
+ * results are bit-equal to the reference's arithmetic.
+ * mcs 0..7 = Bpsk_1_2, Bpsk_3_4, Qpsk_1_2, Qpsk_3_4, Qam16_1_2, Qam16_3_4,
+ * Qam64_2_3, Qam64_3_4 (lib.rs:223-282).
+ * Tail rule: the decoder reads 16*(n_traceback + ceil(n_data_bits/8)) - 4
+ * depunctured values, 76..164 more than the frame has. The reference reads
+ * whatever earlier frames left in its array (never cleared), and past its
+ * end for the largest frames. Here every such position reads as bit value
+ * 0 (not an erasure): each frame decodes as a freshly constructed
+ * reference Decoder would, for any frame size. With a 3/4 or 2/3 rate the
+ * last PSDU byte can still come out wrong for some scrambler seeds (the
+ * scrambled pad bits and this tail are no codeword, and the traceback is
+ * short); the reference does the same, or worse, on its stale tail.
+ * The SIGNAL field (frame_equalizer.rs:121-175) is this decode at
+ * (mcs 0, psdu 0) on the 48 BPSK indices, first 24 decoded bits, followed
+ * by fsdr_wlan_signal_field.
+ * _create/_destroy: the handle owns its device buffers (descriptor upload,
+ *   the staging of _host). Creating needs no device. One handle serves one
+ *   stream at a time.
+ * _decode_dev: `frames` is a host array, free for reuse on return. Frame i
+ *   reads 48*n_symbols index bytes at d_syms + sym_off, writes psdu_size+2
+ *   descrambled bytes at d_out_bytes + out_off, if d_dec_bytes is not NULL
+ *   the ceil(n_data_bits/8) raw Viterbi bytes (before descrambling, MSB =
+ *   earlier bit) at d_dec_bytes + dec_off, and d_crc_ok[i] = 0 or 1.
+ *   Nothing else is written; output ranges must not overlap (not
+ *   checked). Asynchronous on `stream`. FSDR_ERR_INVALID plus an error
+ *   string, and no launch, for mcs > 7, psdu_size > 1528 or more than 511
+ *   symbols (decoder.rs:157, lib.rs:43-45) in any frame, or a NULL
+ *   pointer; n_frames == 0 is a successful no-op. Validation precedes the
+ *   device check.
+ * _decode_host: the same over host spans, synchronous; only the frames'
+ *   own ranges of out_bytes and dec_bytes are written.
+ * Host-only: _frame_param is FrameParam::new (lib.rs:324-343, psdu_size
+ *   <= 4095). _deinterleave_map: out[k] = second[first[k]] of decoder.rs:
+ *   50-64, n_cbps entries, read off the kernel's index map.
+ *   _depuncture_map: for depunctured positions first .. first+count-1 of
+ *   a frame of n_symbols, the kernel's source of each value: 8*byte + bit
+ *   into the frame's index bytes, -1 for an erasure, -2 past the frame
+ *   (reads 0). _signal_field: *found = 0 where the reference returns None
+ *   (parity over bits 0..16 against bit 17, unknown rate in bits 0..3),
+ *   else 1 with mcs and the length from bits 5..16; bits24 holds one bit
+ *   per byte, nonzero = 1. */
+typedef struct fsdr_wlan_decoder fsdr_wlan_decoder;
+typedef struct {
+    uint32_t mcs;
+    uint32_t psdu_size;
+    size_t   sym_off, out_off, dec_off; /* bytes; dec_off unused if NULL */
+} fsdr_wlan_frame;
+fsdr_wlan_decoder* fsdr_wlan_decoder_create(void);
+void fsdr_wlan_decoder_destroy(fsdr_wlan_decoder* dec);
+int fsdr_wlan_decode_dev(fsdr_wlan_decoder* dec, const void* d_syms,
+                         const fsdr_wlan_frame* frames, size_t n_frames,
+                         void* d_out_bytes, void* d_dec_bytes,
+                         void* d_crc_ok, void* stream);
+int fsdr_wlan_decode_host(fsdr_wlan_decoder* dec, const uint8_t* syms,
+                          const fsdr_wlan_frame* frames, size_t n_frames,
+                          uint8_t* out_bytes, uint8_t* dec_bytes,
+                          uint8_t* crc_ok);
+int fsdr_wlan_frame_param(unsigned mcs, size_t psdu_size, size_t* n_symbols,
+                          size_t* n_data_bits, size_t* n_pad);
+int fsdr_wlan_deinterleave_map(unsigned mcs, uint16_t* out);
+int fsdr_wlan_depuncture_map(unsigned mcs, size_t n_symbols, size_t first,
+                             size_t count, int32_t* out);
+int fsdr_wlan_signal_field(const uint8_t* bits24, int* found, unsigned* mcs,
+                           size_t* psdu_size);
+
 /* MFMA-loop microbenchmark (diagnostics; tools/mfma_ubench.py): times
  * the chain kernel's inner MFMA loop on LDS staged once. */
 int fsdr_mfma_ubench(int grid, int iters, double* tflops, void* stream);

@@ -5,7 +5,8 @@ shapes, the standalone FFT kernel, and the PFB synthesizer (fused and
 staged path per shape, plus the channelizer at the same shape for
 context). Prints TF/s or GB/s vs peak. --synth runs the PFB synthesizer
 part only, --arb the PFB arbitrary-rate resampler part only, --iir the IIR
-filter part only, --lora the LoRa FFT demodulator part only."""
+filter part only, --lora the LoRa FFT demodulator part only, --wlan-decode
+the WLAN frame decoder part only."""
 import ctypes
 import os
 import sys
@@ -263,10 +264,65 @@ def lora_lines(lib, st, d_out, S, rounds=5):
     lib.fsdr_dev_free(d_mag)
 
 
+def wlan_decode_lines(lib, st, rounds=5):
+    """WLAN frame decoder over device-resident batches of equal frames:
+    Bpsk_1_2 and Qam64_3_4, psdu 100 and 1500, batches of 1, 256, 4096 and
+    16384 frames, plus a sweep over powers of two at Bpsk_1_2 / psdu 100 to
+    find where the time per call stops being flat. The index bytes are
+    uniformly random (the kernel's work does not depend on the data). One
+    timing is one fsdr_wlan_decode_dev call between two events (descriptor
+    upload included); 2 warm-up calls, then `rounds` timings; median and
+    range, frames/s, decoded Mbit/s (n_data_bits per frame) and trellis
+    steps/s (8 per output byte, n_traceback bytes of run-in, 2 less at the
+    start)."""
+    traceback = {0: 5, 7: 10}
+    dec = fa.WlanDecoder()
+    g = torch.Generator(device="cuda").manual_seed(11)
+
+    def run(mcs, psdu, batch):
+        n_sym, n_bits, _ = fa.wlan_frame_param(mcs, psdu)
+        n_bytes = (n_bits + 7) // 8
+        steps = 8 * (traceback[mcs] + n_bytes) - 2
+        syms = torch.randint(0, 256, (batch * 48 * n_sym,), generator=g,
+                             device="cuda", dtype=torch.uint8)
+        out = torch.empty(batch * (psdu + 2), dtype=torch.uint8,
+                          device="cuda")
+        crc = torch.empty(batch, dtype=torch.uint8, device="cuda")
+        descs = dec._descs([(mcs, psdu, i * 48 * n_sym, i * (psdu + 2), 0)
+                            for i in range(batch)])
+
+        def call():
+            rc = lib.fsdr_wlan_decode_dev(dec._h, syms.data_ptr(), descs,
+                                          batch, out.data_ptr(), None,
+                                          crc.data_ptr(), st.cuda_stream)
+            assert rc == 0, lib.fsdr_last_error()
+
+        v = sorted(timeit(call, reps=1, warm=2) for _ in range(rounds))
+        med = v[len(v) // 2]
+        name = {0: "Bpsk_1_2", 7: "Qam64_3_4"}[mcs]
+        print(f"{name:9s} psdu {psdu:4d} x {batch:5d}: {med:8.3f} ms median "
+              f"of {rounds} [{v[0]:.3f}..{v[-1]:.3f}]  "
+              f"{batch / med * 1e3:11.0f} frames/s  "
+              f"{batch * n_bits / med / 1e3:9.1f} Mbit/s decoded  "
+              f"{batch * steps / med / 1e6:8.2f} G trellis steps/s")
+        return med
+
+    for mcs in (0, 7):
+        for psdu in (100, 1500):
+            for batch in (1, 256, 4096, 16384):
+                run(mcs, psdu, batch)
+    print("sweep, Bpsk_1_2 psdu 100:")
+    for k in range(0, 15):
+        run(0, 100, 1 << k)
+
+
 def main():
     lib = fa.lib()
     fa.set_device(0)
     st = torch.cuda.current_stream()
+    if "--wlan-decode" in sys.argv[1:]:
+        wlan_decode_lines(lib, st)
+        return
     S = 1 << 26
     d_in = ctypes.c_void_p()
     d_out = ctypes.c_void_p()
