@@ -148,6 +148,8 @@ def _load():
     lib.fsdr_moving_avg_create.restype = vp
     lib.fsdr_pfb_channelizer_create.restype = vp
     lib.fsdr_pfb_channelizer_create.argtypes = [sz, f32p, sz, ctypes.c_float]
+    lib.fsdr_pfb_channelizer_window_map.restype = None
+    lib.fsdr_pfb_channelizer_window_map.argtypes = [sz, sz, vp]
     lib.fsdr_pfb_channelizer_stream_dev.restype = ctypes.c_int
     lib.fsdr_pfb_channelizer_stream_dev.argtypes = [vp, vp, sz, vp, sz,
                                                     vp, ctypes.POINTER(sz),
@@ -728,64 +730,65 @@ class PfbChannelizer(Filter):
         super().__init__(_load().fsdr_pfb_channelizer_create(
             num_channels, p, self._taps_keep.size, oversample_rate))
 
-    def stream(self, chunk):
-        """Feed one host chunk through the stateful streaming path;
-        returns ([num_channels, produced] array, consumed). Unconsumed
-        samples must be re-presented by the caller (slab semantics)."""
+    def _call(self, fn, x, cap, with_consumed):
         lib = _load()
-        chunk = np.ascontiguousarray(chunk, CF32)
-        cap = max(1, (chunk.size + self.n * self._tpf()) // self.decim)
         d_in = ctypes.c_void_p()
         d_out = ctypes.c_void_p()
-        _check(lib.fsdr_dev_alloc(ctypes.byref(d_in), chunk.size * 8))
-        _check(lib.fsdr_dev_alloc(ctypes.byref(d_out), self.n * cap * 8))
+        _check(lib.fsdr_dev_alloc(ctypes.byref(d_in), x.size * 8 + 8))
+        _check(lib.fsdr_dev_alloc(ctypes.byref(d_out), self.n * cap * 8 + 8))
         try:
-            _check(lib.fsdr_memcpy_h2d(
-                d_in, ctypes.c_void_p(chunk.ctypes.data), chunk.size * 8))
+            if x.size:
+                _check(lib.fsdr_memcpy_h2d(
+                    d_in, ctypes.c_void_p(x.ctypes.data), x.size * 8))
             prod = ctypes.c_size_t()
             cons = ctypes.c_size_t()
-            _check(lib.fsdr_pfb_channelizer_stream_dev(
-                self._h, d_in, chunk.size, d_out, cap, None,
-                ctypes.byref(prod), ctypes.byref(cons)))
+            tail = ((ctypes.byref(prod), ctypes.byref(cons))
+                    if with_consumed else (ctypes.byref(prod),))
+            _check(fn(self._h, d_in, x.size, d_out, cap, None, *tail))
             _check(lib.fsdr_synchronize())
             out = np.zeros(self.n * cap, CF32)
-            _check(lib.fsdr_memcpy_d2h(ctypes.c_void_p(out.ctypes.data),
-                                       d_out, self.n * cap * 8))
+            if out.size:
+                _check(lib.fsdr_memcpy_d2h(ctypes.c_void_p(out.ctypes.data),
+                                           d_out, self.n * cap * 8))
             return (out.reshape(self.n, cap)[:, :prod.value], cons.value)
         finally:
             lib.fsdr_dev_free(d_in)
             lib.fsdr_dev_free(d_out)
 
+    def stream(self, chunk, out_cap=None):
+        """Feed one host chunk through the stateful streaming path;
+        returns ([num_channels, produced] array, consumed). out_cap is the
+        room per channel (default: every available step). Unconsumed
+        samples must be re-presented by the caller (slab semantics)."""
+        chunk = np.ascontiguousarray(chunk, CF32)
+        if out_cap is None:
+            out_cap = max(1, (chunk.size + self.n * self._tpf())
+                          // self.decim)
+        return self._call(_load().fsdr_pfb_channelizer_stream_dev, chunk,
+                          out_cap, True)
+
     def _tpf(self):
         return -(-self._taps_keep.size // self.n)
 
-    def run(self, inp):
+    def run(self, inp, out_cap=None):
         """Bulk one-shot from zero state over a host span; returns an
-        array of shape [num_channels, produced]."""
-        lib = _load()
+        array of shape [num_channels, produced], at most out_cap steps
+        (default: every available step)."""
         inp = np.ascontiguousarray(inp, CF32)
-        tpf = self._tpf()
-        cap = max(1, (inp.size - self.n * tpf) // self.decim)
-        d_in = ctypes.c_void_p()
-        d_out = ctypes.c_void_p()
-        _check(lib.fsdr_dev_alloc(ctypes.byref(d_in), inp.size * 8))
-        _check(lib.fsdr_dev_alloc(ctypes.byref(d_out), self.n * cap * 8))
-        try:
-            _check(lib.fsdr_memcpy_h2d(d_in,
-                                       ctypes.c_void_p(inp.ctypes.data),
-                                       inp.size * 8))
-            prod = ctypes.c_size_t()
-            _check(lib.fsdr_pfb_channelizer_run_dev(
-                self._h, d_in, inp.size, d_out, cap, None,
-                ctypes.byref(prod)))
-            _check(lib.fsdr_synchronize())
-            out = np.zeros(self.n * cap, CF32)
-            _check(lib.fsdr_memcpy_d2h(ctypes.c_void_p(out.ctypes.data),
-                                       d_out, self.n * cap * 8))
-            return out.reshape(self.n, cap)[:, :prod.value]
-        finally:
-            lib.fsdr_dev_free(d_in)
-            lib.fsdr_dev_free(d_out)
+        if out_cap is None:
+            out_cap = max(1, (inp.size - self.n * self._tpf()) // self.decim)
+        return self._call(_load().fsdr_pfb_channelizer_run_dev, inp,
+                          out_cap, False)[0]
+
+
+def pfb_channelizer_window_map(taps_per_filter, q):
+    """src[w]: which of its window's pushes (0 = first fill push) slice
+    position w (0 = oldest) of a channelizer window holds after
+    taps_per_filter fill pushes and q more, -1 for a hole — the map the
+    start-up kernel reads through. Needs no GPU."""
+    src = np.zeros(taps_per_filter, np.int64)
+    _load().fsdr_pfb_channelizer_window_map(taps_per_filter, q, _c(src))
+    return src
 
 
 def pfb_synthesizer_count(num_channels, taps_per_filter, pushes,

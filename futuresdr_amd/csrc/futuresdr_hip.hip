@@ -2273,6 +2273,64 @@ __global__ void k_pfb_dots(const float2* __restrict__ in,
     }
 }
 
+/* Start-up steps. The reference's windows are WindowBuffer::new(tpf,
+ * false) (channelizer.rs:117, window_buffer.rs:13-32): fill push k of a
+ * window lands at slot 2k mod tpf, so the just-filled window is a shuffle
+ * of its fill pushes (even tpf: half the slots stay zero and half the
+ * pushes are overwritten; odd tpf: a permutation), and it is the clean
+ * oldest->newest window of k_pfb_dots only once tpf ordinary pushes have
+ * rewritten every slot. Window b takes stream pushes p = (N-1-b) + m*N,
+ * m = 0, 1, ...; with L = tpf fill pushes and q < L pushes after them,
+ * slice position w (0 = oldest) is slot x = (q+w) mod L, which holds push
+ * ordinal m = L+x once rewritten (x < q), else the last fill push with
+ * 2m = x (mod L), else nothing. Returns m, or -1 for a hole (reads as 0);
+ * q >= L is the steady state m = q+w. */
+__host__ __device__ static inline int pfb_chan_window_src(int L, int q,
+                                                          int w) {
+    if (q >= L) return q + w;
+    const int x = (q + w) % L;
+    if (x < q) return L + x;
+    if (((x + L) & 1) == 0) return (x + L) / 2;
+    if ((x & 1) == 0) return x / 2;
+    return -1;
+}
+
+/* The steps whose push count P = p_before + (k+1)*D is still below
+ * 2*N*tpf, rewritten after k_pfb_dots: its sum with every window read
+ * through pfb_chan_window_src, in the same newest-first order (the
+ * launch order does not matter to the result: this kernel reads `in`
+ * only). q = (P+b)/N - tpf
+ * pushes have followed window b's fill. A start-up step reaches back to
+ * push 0, so `in` holds the whole stream so far (bufbase = 0 for the
+ * bulk entry; the streaming entry keeps it that long). */
+__global__ void k_pfb_dots_startup(const float2* __restrict__ in,
+                                   float2* __restrict__ fb,
+                                   const float* __restrict__ part, int N,
+                                   int tpf, int D, long long steps,
+                                   long long p_before, long long bufbase) {
+    long long id = blockIdx.x * (long long)blockDim.x + threadIdx.x;
+    long long total = steps * N;
+    long long stride = (long long)gridDim.x * blockDim.x;
+    for (; id < total; id += stride) {
+        long long k = id / N;
+        int b = (int)(id - k * N);
+        long long P = p_before + (k + 1) * (long long)D;
+        int base = (int)(((N - 1 - P) % N + N) % N);
+        int i = ((b - base - 1) % N + N) % N;
+        int q = (int)((P + b) / N) - tpf;
+        float sre = 0.f, sim = 0.f;
+        for (int j = 0; j < tpf; j++) {
+            int m = pfb_chan_window_src(tpf, q, tpf - 1 - j);
+            if (m < 0) continue;
+            float2 x = in[(N - 1 - b) + (long long)m * N - bufbase];
+            float tap = part[i * tpf + j];
+            sre = fmaf(x.x, tap, sre);
+            sim = fmaf(x.y, tap, sim);
+        }
+        fb[k * N + b] = make_float2(sre, sim);
+    }
+}
+
 __global__ void k_pfb_scatter(const float2* __restrict__ ifft,
                               float2* __restrict__ out, int N,
                               long long steps, long long cap) {
@@ -4207,7 +4265,9 @@ struct fsdr_filter {
     } pfb;
 
     /* PFB channelizer. Streaming state: the last channels*tpf consumed
-     * samples and the total pushes (channelizer.rs round-robin state). */
+     * samples (every consumed sample while pushes < 2*channels*tpf, for
+     * the start-up steps) and the total pushes (channelizer.rs
+     * round-robin state). */
     struct {
         size_t decim = 1;    /* channels / oversample_rate */
         dev_buf taps;        /* part[i][c] = taps[i + c*channels] */
@@ -6301,6 +6361,45 @@ extern "C" int fsdr_filter_host(fsdr_filter* f, const void* in, size_t n_in,
     return FSDR_OK;
 }
 
+extern "C" void fsdr_pfb_channelizer_window_map(size_t taps_per_filter,
+                                                size_t q, long long* src) {
+    if (!src) return;
+    for (size_t w = 0; w < taps_per_filter; w++)
+        src[w] = pfb_chan_window_src((int)taps_per_filter, (int)q, (int)w);
+}
+
+/* dots of `steps` output steps after p_before pushes into ch.dots:
+ * k_pfb_dots over all of them, launched as it always was, then the
+ * leading steps with fewer than 2*N*tpf pushes are rewritten through the
+ * start-up map by a small launch of their own (as the synthesizer's
+ * start-up rows are). d_in[0] is stream sample `bufbase`; 0 while any
+ * step is a start-up one. */
+static int pfb_chan_dots(fsdr_filter* f, const float2* d_in, size_t steps,
+                         size_t p_before, size_t bufbase, hipStream_t st) {
+    auto& ch = f->chan;
+    const size_t N = f->pfb.channels, tpf = f->pfb.tpf, D = ch.decim;
+    const size_t steady_at = 2 * N * tpf;
+    hipLaunchKernelGGL(k_pfb_dots,
+                       dim3(grid_for((long long)(steps * N), 256)),
+                       dim3(256), 0, st, d_in, ch.dots.as<float2>(),
+                       ch.taps.as<const float>(), (int)N, (int)tpf, (int)D,
+                       (long long)steps, (long long)p_before,
+                       (long long)bufbase);
+    HIP_TRY(hipGetLastError());
+    if (p_before + D < steady_at) {
+        const size_t n_start =
+            std::min(steps, (steady_at - p_before + D - 1) / D - 1);
+        hipLaunchKernelGGL(k_pfb_dots_startup,
+                           dim3(grid_for((long long)(n_start * N), 256)),
+                           dim3(256), 0, st, d_in, ch.dots.as<float2>(),
+                           ch.taps.as<const float>(), (int)N, (int)tpf,
+                           (int)D, (long long)n_start, (long long)p_before,
+                           (long long)bufbase);
+        HIP_TRY(hipGetLastError());
+    }
+    return FSDR_OK;
+}
+
 extern "C" int fsdr_pfb_channelizer_run_dev(fsdr_filter* f,
                                             const void* d_in, size_t n_in,
                                             void* d_out,
@@ -6322,14 +6421,9 @@ extern "C" int fsdr_pfb_channelizer_run_dev(fsdr_filter* f,
     if (steps == 0) return FSDR_OK;
     HIP_TRY(ch.dots.ensure(steps * N * 8));
     HIP_TRY(ch.spectra.ensure(steps * N * 8));
-    hipLaunchKernelGGL(k_pfb_dots,
-                       dim3(grid_for((long long)(steps * N), 256)),
-                       dim3(256), 0, st, (const float2*)d_in,
-                       ch.dots.as<float2>(), ch.taps.as<const float>(), (int)N,
-                       (int)tpf, (int)D, (long long)steps,
-                       (long long)prefill, (long long)0);
-    HIP_TRY(hipGetLastError());
-    int rc = launch_fft(f->pfb.ifft, ch.dots.ptr, ch.spectra.ptr, steps, st);
+    int rc = pfb_chan_dots(f, (const float2*)d_in, steps, prefill, 0, st);
+    if (rc) return rc;
+    rc = launch_fft(f->pfb.ifft, ch.dots.ptr, ch.spectra.ptr, steps, st);
     if (rc) return rc;
     hipLaunchKernelGGL(k_pfb_scatter,
                        dim3(grid_for((long long)(steps * N), 256)),
@@ -6343,8 +6437,10 @@ extern "C" int fsdr_pfb_channelizer_run_dev(fsdr_filter* f,
 /* Streaming channelizer: stateful like the reference block — carries
  * the round-robin window contents (the last N*tpf CONSUMED samples) and
  * the push count across calls, consuming in D-sample quanta after the
- * N*tpf prefill (channelizer.rs:156-212). The unconsumed chunk
- * remainder stays with the caller (pair with fsdr_ring's
+ * N*tpf prefill (channelizer.rs:156-212). While the stream is younger
+ * than 2*N*tpf pushes it carries every consumed sample instead, since a
+ * start-up step reads fill pushes back to the first. The unconsumed
+ * chunk remainder stays with the caller (pair with fsdr_ring's
  * release_consumed carry). All work is enqueued on `stream`; use one
  * stream per filter. */
 extern "C" int fsdr_pfb_channelizer_stream_dev(
@@ -6361,7 +6457,7 @@ extern "C" int fsdr_pfb_channelizer_stream_dev(
     size_t N = f->pfb.channels, tpf = f->pfb.tpf, D = ch.decim;
     size_t prefill = N * tpf, W = N * tpf;
     size_t p = ch.pushes;
-    size_t T = p < W ? p : W;
+    size_t T = p < 2 * W ? p : W;
     size_t fill = p < prefill ? std::min(prefill - p, n) : 0;
     size_t steps = (p + n >= prefill) ? (p + n - prefill) / D -
                                             (p > prefill ? (p - prefill) / D
@@ -6383,15 +6479,10 @@ extern "C" int fsdr_pfb_channelizer_stream_dev(
     if (steps) {
         HIP_TRY(ch.dots.ensure(steps * N * 8));
         HIP_TRY(ch.spectra.ensure(steps * N * 8));
-        hipLaunchKernelGGL(k_pfb_dots,
-                           dim3(grid_for((long long)(steps * N), 256)),
-                           dim3(256), 0, st, ch.work.as<const float2>(),
-                           ch.dots.as<float2>(), ch.taps.as<const float>(),
-                           (int)N, (int)tpf, (int)D, (long long)steps,
-                           (long long)(p + fill), (long long)(p - T));
-        HIP_TRY(hipGetLastError());
-        int rc =
-            launch_fft(f->pfb.ifft, ch.dots.ptr, ch.spectra.ptr, steps, st);
+        int rc = pfb_chan_dots(f, ch.work.as<const float2>(), steps,
+                               p + fill, p - T, st);
+        if (rc) return rc;
+        rc = launch_fft(f->pfb.ifft, ch.dots.ptr, ch.spectra.ptr, steps, st);
         if (rc) return rc;
         hipLaunchKernelGGL(k_pfb_scatter,
                            dim3(grid_for((long long)(steps * N), 256)),
@@ -6400,9 +6491,10 @@ extern "C" int fsdr_pfb_channelizer_stream_dev(
                            (long long)out_cap_per_chan);
         HIP_TRY(hipGetLastError());
     }
-    /* new hist = last min(W, T+cons) samples of the work buffer */
-    size_t newT = std::min(W, T + cons);
-    HIP_TRY(ch.hist.ensure(W * 8));
+    /* new hist = the whole work buffer while the stream is young, its
+     * last W samples from then on */
+    size_t newT = p + cons < 2 * W ? T + cons : W;
+    HIP_TRY(ch.hist.ensure(2 * W * 8));
     HIP_TRY(hipMemcpyAsync(ch.hist.ptr,
                            ch.work.as<char>() + (T + cons - newT) * 8,
                            newT * 8, hipMemcpyDeviceToDevice, st));

@@ -328,13 +328,32 @@ int fsdr_rotator_dev(const void* d_in, void* d_out, size_t n,
  * Supports any oversample_rate = N/i (decimation D = N/oversample,
  * channelizer.rs:100-105); num_channels must be a power of two in
  * [4,4096] (FFT kernel). Output is channel-major:
- * out[c*out_cap_per_chan + k]. run_dev = bulk from zero state;
+ * out[c*out_cap_per_chan + k]. The first N*tpf samples (tpf =
+ * ceil(n_taps/N)) only fill the windows; every D samples after them give
+ * one output step, min(out_cap_per_chan, remaining/D) steps per call, and
+ * nothing is written past them. run_dev = bulk from zero state;
  * stream_dev carries the round-robin window state across calls and
  * consumes in D quanta after the N*tpf prefill (pair with the ring's
- * release_consumed carry for exact arbitrary-chunk streaming). */
+ * release_consumed carry for exact arbitrary-chunk streaming). Where the
+ * reference needs one work() call to finish the fill and a second to
+ * produce, one call here does both.
+ * Start-up steps. The reference's windows are WindowBuffer::new(tpf,
+ * false): fill push k of a window lands at slot 2k mod tpf
+ * (window_buffer.rs:23-32), so a just-filled window is a shuffle of its
+ * fill pushes (even tpf: half the slots still zero, half the pushes
+ * lost; odd tpf: a permutation) until tpf further pushes have rewritten
+ * every slot. Output step k is the textbook polyphase sum only once
+ * (k+1)*D >= tpf*N; the tpf*N/D - 1 steps in front of it are computed
+ * from the shuffled windows, as the reference computes them (none when
+ * tpf = 1). stream_dev keeps every consumed sample until the stream has
+ * 2*N*tpf pushes for this. _window_map: src[w] = which of its window's
+ * pushes (0 = first fill push) slice position w, 0 = oldest, holds after
+ * tpf fill pushes and q more, -1 for a hole; host-only. */
 fsdr_filter* fsdr_pfb_channelizer_create(size_t num_channels,
                                          const float* taps, size_t n_taps,
                                          float oversample_rate);
+void fsdr_pfb_channelizer_window_map(size_t taps_per_filter, size_t q,
+                                     long long* src);
 int fsdr_pfb_channelizer_run_dev(fsdr_filter* f, const void* d_in,
                                  size_t n_in, void* d_out,
                                  size_t out_cap_per_chan, void* stream,

@@ -511,19 +511,29 @@ size_t oracle_pfb_channelizer(size_t N, size_t D,
         for (size_t t = i; t < n_taps; t += N) part[i * tpf + cnt++] = taps[t];
         /* remaining entries stay 0 (the pad) */
     }
-    /* window buffers: w[b][0..tpf) oldest->newest (window_buffer.rs) */
-    ocf32* win = (ocf32*)calloc(N * tpf, sizeof(ocf32));
+    /* window buffers as WindowBuffer::new(tpf, false) keeps them
+     * (window_buffer.rs:11-44): a doubled circular buffer per window,
+     * start_idx, num_samples_missing. A fill push lands at
+     * (start_idx - missing) mod tpf, so the just-filled window is a
+     * shuffle, and only tpf more pushes make it oldest->newest. */
+    ocf32* win = (ocf32*)calloc(N * 2 * tpf, sizeof(ocf32));
+    size_t* start = (size_t*)calloc(N, sizeof(size_t));
     size_t* missing = (size_t*)malloc(N * sizeof(size_t));
     for (size_t b = 0; b < N; b++) missing[b] = tpf;
+#define PFB_WIN_PUSH(b_, s_)                                                \
+    do {                                                                    \
+        size_t at_ = (start[b_] + tpf - missing[b_] % tpf) % tpf;           \
+        win[(b_) * 2 * tpf + at_] = (s_);                                   \
+        win[(b_) * 2 * tpf + at_ + tpf] = (s_);                             \
+        if (missing[b_]) missing[b_]--;                                     \
+        start[b_] = (start[b_] + 1) % tpf;                                  \
+    } while (0)
     size_t base = N - 1;
     size_t consumed = 0;
     /* prefill (:156-180) */
     int all_filled = 0;
     while (!all_filled && consumed < n_in) {
-        ocf32* w = win + base * tpf;
-        memmove(w, w + 1, (tpf - 1) * sizeof(ocf32));
-        w[tpf - 1] = in[consumed];
-        if (missing[base]) missing[base]--;
+        PFB_WIN_PUSH(base, in[consumed]);
         base = (base == 0) ? N - 1 : base - 1;
         consumed++;
         all_filled = 1;
@@ -539,14 +549,13 @@ size_t oracle_pfb_channelizer(size_t N, size_t D,
         ocf32* fb = (ocf32*)malloc(N * sizeof(ocf32));
         for (size_t k = 0; k < steps; k++) {
             for (size_t j = 0; j < D; j++) { /* :185-191 */
-                ocf32* w = win + base * tpf;
-                memmove(w, w + 1, (tpf - 1) * sizeof(ocf32));
-                w[tpf - 1] = in[consumed + k * D + j];
+                PFB_WIN_PUSH(base, in[consumed + k * D + j]);
                 base = (base == 0) ? N - 1 : base - 1;
             }
             for (size_t i = 0; i < N; i++) { /* :193-202 */
                 size_t b = (base + i + 1) % N;
-                const ocf32* w = win + b * tpf;
+                /* get_as_slice (window_buffer.rs:35-39) */
+                const ocf32* w = win + b * 2 * tpf + start[b];
                 float sre = 0.f, sim = 0.f;
                 for (size_t t = 0; t < tpf; t++) {
                     float tap = part[i * tpf + (tpf - 1 - t)];
@@ -566,8 +575,10 @@ size_t oracle_pfb_channelizer(size_t N, size_t D,
         free(fr);
         free(fb);
     }
+#undef PFB_WIN_PUSH
     free(part);
     free(win);
+    free(start);
     free(missing);
     return produced;
 }

@@ -152,6 +152,10 @@ void oracle_moving_avg(size_t width, float decay_factor, size_t history,
  * sub-filters from partition_filter_taps (utilities.rs:5-25, taps NOT
  * reversed in partitioning; FirFilter then applies them reversed), one
  * unnormalized inverse FFT of size num_channels per output step.
+ * The windows are WindowBuffer::new(tpf, false) as written (doubled
+ * circular buffer, start_idx, num_samples_missing): fill push k of a
+ * window lands at slot 2k mod tpf, so the first tpf*N/D - 1 output steps
+ * see a shuffled window (some early samples lost, holes zero).
  * One-shot from zero state: prefills, then produces
  * min(out_cap_per_chan, remaining/decimation) samples per channel.
  * out is channel-major: out[c*out_cap_per_chan + k]. decimation_factor =

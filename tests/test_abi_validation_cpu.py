@@ -44,7 +44,9 @@ def test_pfb_constraints(fsdr):
     p = taps.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
     assert not fsdr.lib().fsdr_pfb_channelizer_create(2, p, 32, 1.0)
     assert not fsdr.lib().fsdr_pfb_channelizer_create(8, p, 4, 1.0)
-    assert not fsdr.lib().fsdr_pfb_channelizer_create(8, p, 32, 2.0)
+    # :100-103: N % oversample_rate == 0 (2.0 divides 8 and is accepted
+    # where a device is present; 3.0 is refused everywhere)
+    assert not fsdr.lib().fsdr_pfb_channelizer_create(8, p, 32, 3.0)
 
 
 def test_fft_len_gate(fsdr):
