@@ -6,6 +6,7 @@ extension; there is NO CPU fallback here — if the shared library or a HIP
 device is missing, calls raise. The CPU restatement used for parity lives
 in oracle/ (test infrastructure) and is never imported by this package.
 """
+import collections
 import ctypes
 import os
 import subprocess
@@ -138,6 +139,20 @@ def _load():
     lib.fsdr_wlan_signal_field.argtypes = [vp, ctypes.POINTER(ctypes.c_int),
                                            ctypes.POINTER(ctypes.c_uint),
                                            szp]
+    lib.fsdr_wlan_equalizer_create.restype = vp
+    lib.fsdr_wlan_equalizer_create.argtypes = []
+    lib.fsdr_wlan_equalizer_destroy.restype = None
+    lib.fsdr_wlan_equalizer_destroy.argtypes = [vp]
+    lib.fsdr_wlan_equalize_dev.restype = ctypes.c_int
+    lib.fsdr_wlan_equalize_dev.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp]
+    lib.fsdr_wlan_equalize_host.restype = ctypes.c_int
+    lib.fsdr_wlan_equalize_host.argtypes = [vp, vp, vp, sz, vp, vp, vp]
+    lib.fsdr_wlan_demap.restype = ctypes.c_int
+    lib.fsdr_wlan_demap.argtypes = [ctypes.c_uint, vp, sz, vp]
+    lib.fsdr_wlan_pilot_polarity.restype = ctypes.c_int
+    lib.fsdr_wlan_pilot_polarity.argtypes = [sz, sz, vp]
+    lib.fsdr_wlan_carrier_map.restype = ctypes.c_int
+    lib.fsdr_wlan_carrier_map.argtypes = [vp]
     lib.fsdr_firdes_kaiser_multirate_f32.restype = sz
     lib.fsdr_firdes_kaiser_multirate_f32.argtypes = [sz, sz, sz,
                                                      ctypes.c_double, f32p,
@@ -1423,6 +1438,222 @@ class WlanDecoder:
                 r += (dec[do:do + (nd + 7) // 8].copy(),)
             res.append(r)
         return res
+
+
+class _WlanEqFrame(ctypes.Structure):
+    _fields_ = [
+        ("sym_off", ctypes.c_size_t),
+        ("n_avail", ctypes.c_uint32),
+        ("idx_off", ctypes.c_size_t),
+        ("eq_off", ctypes.c_size_t),
+    ]
+
+
+class _WlanEqInfo(ctypes.Structure):
+    _fields_ = [
+        ("found", ctypes.c_uint32),
+        ("mcs", ctypes.c_uint32),
+        ("psdu_size", ctypes.c_uint32),
+        ("n_symbols", ctypes.c_uint32),
+        ("n_copied", ctypes.c_uint32),
+        ("snr_db", ctypes.c_float),
+    ]
+
+
+WLAN_EQ_INFO_DTYPE = np.dtype([("found", np.uint32), ("mcs", np.uint32),
+                               ("psdu_size", np.uint32),
+                               ("n_symbols", np.uint32),
+                               ("n_copied", np.uint32),
+                               ("snr_db", np.float32)])
+
+WlanEqInfo = collections.namedtuple(
+    "WlanEqInfo", "found mcs psdu_size n_symbols n_copied snr_db")
+
+
+def _wlan_eq_info(rec):
+    return WlanEqInfo(bool(rec["found"]), int(rec["mcs"]),
+                      int(rec["psdu_size"]), int(rec["n_symbols"]),
+                      int(rec["n_copied"]), float(rec["snr_db"]))
+
+
+def wlan_demap(mcs, z):
+    """Constellation indices of the values z by the reference's
+    Modulation::demap (lib.rs:177-218), the function the equalizer kernel
+    uses. Needs no device."""
+    if mcs < 0:
+        raise FsdrError("wlan: mcs must be in [0,7]")
+    z = np.ascontiguousarray(z, CF32).reshape(-1)
+    out = np.zeros(z.size, np.uint8)
+    _check(_load().fsdr_wlan_demap(mcs, _c(z), z.size, _c(out)))
+    return out
+
+
+def wlan_pilot_polarity(count, first=0):
+    """POLARITY[(first + i) % 127] for i < count as +1 / -1 (lib.rs:365),
+    generated from the scrambler as the kernel does. Needs no device."""
+    if count < 0 or first < 0:
+        raise FsdrError("wlan: negative argument")
+    out = np.zeros(count, np.int8)
+    _check(_load().fsdr_wlan_pilot_polarity(first, count, _c(out)))
+    return out
+
+
+def wlan_carrier_map():
+    """Output position of each of the 64 carriers in a symbol's 48 values,
+    -1 for pilots, DC and guards (frame_equalizer.rs:55-57). Needs no
+    device."""
+    out = np.zeros(64, np.int8)
+    _check(_load().fsdr_wlan_carrier_map(_c(out)))
+    return out
+
+
+class WlanEqualizer:
+    """The reference's WLAN FrameEqualizer (examples/wlan src/
+    frame_equalizer.rs) for a batch of frames: channel estimate, pilot
+    phase, SIGNAL field, equalize and demap (see include/futuresdr_hip.h).
+    Input is the plain 64-point FFT of WlanRx.sync_long's stream."""
+
+    def __init__(self):
+        self._h = _load().fsdr_wlan_equalizer_create()
+        if not self._h:
+            raise FsdrError("wlan equalizer create failed: "
+                            + _load().fsdr_last_error().decode())
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            _load().fsdr_wlan_equalizer_destroy(self._h)
+            self._h = None
+
+    @staticmethod
+    def _descs(frames):
+        arr = (_WlanEqFrame * max(1, len(frames)))()
+        for d, f in zip(arr, frames):
+            if min(f) < 0 or f[1] > 0xFFFFFFFF:
+                raise FsdrError("wlan: frame field out of range")
+            d.sym_off, d.n_avail, d.idx_off, d.eq_off = f
+        return arr
+
+    def equalize_dev(self, d_spec, frames, d_idx, d_info, d_eq=None,
+                     stream=None):
+        """Device-pointer path (ints = device addresses), asynchronous on
+        `stream`. frames: (sym_off, n_avail, idx_off, eq_off)."""
+        frames = list(frames)
+        _check(_load().fsdr_wlan_equalize_dev(
+            self._h, ctypes.c_void_p(d_spec), self._descs(frames),
+            len(frames), ctypes.c_void_p(d_idx), ctypes.c_void_p(d_eq or 0),
+            ctypes.c_void_p(d_info), ctypes.c_void_p(stream or 0)))
+
+    def equalize(self, spec, frames, symbols=False):
+        """spec: the cf32 FFT stream; frames: (sym_off, n_avail) pairs in
+        items of it. Returns per frame (info, indices), with symbols=True
+        (info, indices, eq_symbols): info is a WlanEqInfo, indices the
+        48*n_copied constellation indices, eq_symbols as many equalized
+        values."""
+        spec = np.ascontiguousarray(spec, CF32).reshape(-1)
+        descs, off = [], 0
+        for so, na in frames:
+            so, na = int(so), int(na)
+            if so < 0 or na < 0 or so + 64 * na > spec.size:
+                raise FsdrError("wlan: frame outside the spectrum stream")
+            descs.append((so, na, off, off))
+            off += 48 * max(na - 3, 0)
+        if not descs:
+            return []
+        idx = np.zeros(max(off, 1), np.uint8)
+        eqs = np.zeros(max(off, 1), CF32) if symbols else None
+        info = np.zeros(len(descs), WLAN_EQ_INFO_DTYPE)
+        _check(_load().fsdr_wlan_equalize_host(
+            self._h, _c(spec), self._descs(descs), len(descs), _c(idx),
+            _c(eqs) if symbols else None, _c(info)))
+        res = []
+        for rec, (_, _, o, _) in zip(info, descs):
+            n = 48 * int(rec["n_copied"])
+            r = (_wlan_eq_info(rec), idx[o:o + n].copy())
+            if symbols:
+                r += (eqs[o:o + n].copy(),)
+            res.append(r)
+        return res
+
+
+def wlan_frame_spans(tags, frames, n_samples):
+    """(sym_off, n_avail) in the FFT stream of every frame that one
+    WlanRx.sync_long(frame_samples, tags) call produced: tags as passed to
+    it, frames as it returned them, n_samples = frame_samples.size. The
+    rule is the state machine's: a tag with fewer than 448 samples to the
+    next tag (or to the end) yields no frame; a frame yields 128 items plus
+    64 per whole 80 samples behind them. One-shot only: it does not
+    describe a stream fed to sync_long in several calls."""
+    spans, off, j = [], 0, 0
+    for t, (start, _) in enumerate(tags):
+        end = tags[t + 1][0] if t + 1 < len(tags) else n_samples
+        if end - start < 320 + 128 or j >= len(frames):
+            continue
+        n_sym = (end - (start + frames[j][0] + 128)) // 80
+        spans.append((off, 2 + n_sym))
+        off += 128 + 64 * n_sym
+        j += 1
+    return spans
+
+
+def wlan_receive(spec, spans):
+    """Spectra to bytes: equalize the frames `spans` ((sym_off, n_avail)
+    pairs) of the FFT stream `spec`, then decode on the device every frame
+    that is found, complete (n_copied == n_symbols) and within the
+    decoder's limits (psdu <= 1528, <= 511 symbols), reading the index
+    buffer where the equalizer wrote it. Returns per frame (info,
+    psdu_bytes or None, crc_ok)."""
+    lib = _load()
+    spec = np.ascontiguousarray(spec, CF32).reshape(-1)
+    descs, off = [], 0
+    for so, na in spans:
+        so, na = int(so), int(na)
+        if so < 0 or na < 0 or so + 64 * na > spec.size:
+            raise FsdrError("wlan: frame outside the spectrum stream")
+        descs.append((so, na, off, 0))
+        off += 48 * max(na - 3, 0)
+    if not descs:
+        return []
+    info = np.zeros(len(descs), WLAN_EQ_INFO_DTYPE)
+    ptrs = []
+
+    def alloc(nbytes):
+        p = ctypes.c_void_p()
+        _check(lib.fsdr_dev_alloc(ctypes.byref(p), max(1, nbytes)))
+        ptrs.append(p)
+        return p
+
+    try:
+        d_spec, d_idx = alloc(spec.nbytes), alloc(off)
+        d_info = alloc(info.nbytes)
+        _check(lib.fsdr_memcpy_h2d(d_spec, _c(spec), spec.nbytes))
+        eq = WlanEqualizer()  # alive until its work has finished
+        eq.equalize_dev(d_spec.value, descs, d_idx.value, d_info.value)
+        _check(lib.fsdr_synchronize())
+        _check(lib.fsdr_memcpy_d2h(_c(info), d_info, info.nbytes))
+        dec, which, oo = [], [], 0
+        for i, (rec, d) in enumerate(zip(info, descs)):
+            if rec["found"] and rec["n_copied"] == rec["n_symbols"] and \
+                    rec["psdu_size"] <= 1528 and rec["n_symbols"] <= 511:
+                dec.append((int(rec["mcs"]), int(rec["psdu_size"]), d[2],
+                            oo, 0))
+                which.append(i)
+                oo += int(rec["psdu_size"]) + 2
+        out = np.zeros(max(oo, 1), np.uint8)
+        crc = np.zeros(max(len(dec), 1), np.uint8)
+        if dec:
+            d_out, d_crc = alloc(out.nbytes), alloc(crc.nbytes)
+            decoder = WlanDecoder()
+            decoder.decode_dev(d_idx.value, dec, d_out.value, d_crc.value)
+            _check(lib.fsdr_synchronize())
+            _check(lib.fsdr_memcpy_d2h(_c(out), d_out, out.nbytes))
+            _check(lib.fsdr_memcpy_d2h(_c(crc), d_crc, crc.nbytes))
+    finally:
+        for p in ptrs:
+            lib.fsdr_dev_free(p)
+    res = [(_wlan_eq_info(rec), None, False) for rec in info]
+    for k, (i, (_, psdu, _, o, _)) in enumerate(zip(which, dec)):
+        res[i] = (res[i][0], out[o + 2:o + 2 + psdu].copy(), bool(crc[k]))
+    return res
 
 
 def cmul_host(a, b):

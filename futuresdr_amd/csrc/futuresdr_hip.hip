@@ -7679,28 +7679,38 @@ extern "C" int fsdr_wlan_depuncture_map(unsigned mcs, size_t n_symbols,
     return FSDR_OK;
 }
 
-/* frame_equalizer.rs:142-174 */
+/* frame_equalizer.rs:142-174 on a word whose bit i is decoded bit i: parity
+ * over bits 0..16 against bit 17, rate in bits 0..3 (8..15 are the known
+ * ones: mcs 6, 4, 2, 0, 7, 5, 3, 1), length in bits 5..16. Shared by
+ * fsdr_wlan_signal_field and k_wlan_eq_data. */
+__host__ __device__ static inline bool wlan_signal_parse(unsigned bits,
+                                                         unsigned* mcs,
+                                                         unsigned* psdu) {
+    unsigned parity = bits & 0x1ffffu;
+    parity ^= parity >> 16;
+    parity ^= parity >> 8;
+    parity ^= parity >> 4;
+    parity ^= parity >> 2;
+    parity ^= parity >> 1;
+    const unsigned r = bits & 0xfu;
+    if ((parity & 1u) != ((bits >> 17) & 1u) || r < 8) return false;
+    *mcs = (0x13570246u >> (4 * (r - 8))) & 0xfu;
+    *psdu = (bits >> 5) & 0xfffu;
+    return true;
+}
+
 extern "C" int fsdr_wlan_signal_field(const uint8_t* bits24, int* found,
                                       unsigned* mcs, size_t* psdu_size) {
     if (!bits24 || !found) {
         set_err("wlan: null argument");
         return FSDR_ERR_INVALID;
     }
-    unsigned r = 0, bytes = 0, parity = 0;
-    for (int i = 0; i < 17; i++) {
-        const unsigned b = bits24[i] > 0;
-        parity ^= b;
-        if (i < 4) r |= b << i;
-        if (i > 4) bytes |= b << (i - 5);
-    }
-    static const int rate_to_mcs[16] = {-1, -1, -1, -1, -1, -1, -1, -1,
-                                        6,  4,  2,  0,  7,  5,  3,  1};
-    *found = 0;
-    if (parity != (unsigned)(bits24[17] > 0) || rate_to_mcs[r] < 0)
-        return FSDR_OK;
-    *found = 1;
-    if (mcs) *mcs = (unsigned)rate_to_mcs[r];
-    if (psdu_size) *psdu_size = bytes;
+    unsigned bits = 0, m = 0, p = 0;
+    for (int i = 0; i < 18; i++) bits |= (unsigned)(bits24[i] > 0) << i;
+    *found = wlan_signal_parse(bits, &m, &p) ? 1 : 0;
+    if (!*found) return FSDR_OK;
+    if (mcs) *mcs = m;
+    if (psdu_size) *psdu_size = p;
     return FSDR_OK;
 }
 
@@ -7875,6 +7885,495 @@ extern "C" int fsdr_wlan_decode_host(fsdr_wlan_decoder* dec,
     }
     HIP_TRY(hipMemcpy(crc_ok, dec->st_crc.ptr, n_frames,
                       hipMemcpyDeviceToHost));
+    return FSDR_OK;
+}
+
+/* ================= WLAN frame equalizer ================================
+ * examples/wlan FrameEqualizer (src/frame_equalizer.rs) for a batch of
+ * frames: channel estimate from the two long-training symbols, common pilot
+ * phase of every symbol, SIGNAL field, equalize and demap ("WLAN
+ * frame equalizer"). Lane = carrier: a 64-bin symbol is one wavefront. Three
+ * launches on the caller's stream: k_wlan_eq_head (one wave per frame),
+ * k_wlan_decode over the SIGNAL fields at (mcs 0, psdu 0), k_wlan_eq_data
+ * (waves over the data symbols). No LDS, no barrier. */
+
+#define WLAN_EQ_WAVES 4      /* waves per block, both kernels */
+#define WLAN_EQ_SLOT_BLOCKS 8 /* blocks sharing one frame's data symbols */
+#define WLAN_EQ_MAX_SYM 1366  /* FrameParam::new at Bpsk_1_2, psdu 4095 */
+
+/* lib.rs:365: 1 - 2*bit of the x^7+x^4+1 scrambler seeded with all ones,
+ * 127 entries; bit i of {lo, hi} is set where the entry is -1. */
+struct WlanPolarity {
+    unsigned long long lo, hi;
+    constexpr WlanPolarity() : lo(0), hi(0) {
+        unsigned state = 0x7f;
+        for (int i = 0; i < 127; i++) {
+            const unsigned fb = ((state >> 6) ^ (state >> 3)) & 1;
+            state = ((state << 1) & 0x7e) | fb;
+            if (fb) (i < 64 ? lo : hi) |= 1ull << (i & 63);
+        }
+    }
+};
+__host__ __device__ static inline float wlan_polarity(unsigned i) {
+    constexpr WlanPolarity p = WlanPolarity();
+    i %= 127;
+    return (((i < 64 ? p.lo : p.hi) >> (i & 63)) & 1) ? -1.0f : 1.0f;
+}
+
+/* lib.rs:495, the frequency-domain long-training sequence L(-26..26) on
+ * carriers 6..58: half its sign (the reference divides by LONG + LONG), 0
+ * on the other carriers. */
+__host__ __device__ static inline float wlan_long_half(unsigned m) {
+    /* '-' entries of "++--++-+-++++++--++-+-++++0+--++-+-+-----++--+-+-++++",
+     * bit m - 6 */
+    constexpr unsigned long long neg =
+        (1ull << 2) | (1ull << 3) | (1ull << 6) | (1ull << 8) |
+        (1ull << 15) | (1ull << 16) | (1ull << 19) | (1ull << 21) |
+        (1ull << 28) | (1ull << 29) | (1ull << 32) | (1ull << 34) |
+        (1ull << 36) | (1ull << 37) | (1ull << 38) | (1ull << 39) |
+        (1ull << 40) | (1ull << 43) | (1ull << 44) | (1ull << 46) |
+        (1ull << 48);
+    if (m < 6 || m > 58 || m == 32) return 0.0f;
+    return ((neg >> (m - 6)) & 1) ? -0.5f : 0.5f;
+}
+
+/* frame_equalizer.rs:55-57: output position of carrier m, -1 for the
+ * guards, DC and the four pilots. */
+__host__ __device__ static inline int wlan_carrier_out(unsigned m) {
+    if (m < 6 || m > 58 || m == 11 || m == 25 || m == 32 || m == 39 ||
+        m == 53)
+        return -1;
+    return (int)m - 6 - (m > 11) - (m > 25) - (m > 32) - (m > 39) - (m > 53);
+}
+
+/* Modulation::demap, lib.rs:177-218, strict comparisons; the thresholds are
+ * f32 products of the f32 constants. NaN gives 0. */
+__host__ __device__ static inline unsigned wlan_demap(unsigned bpsc, float re,
+                                                      float im) {
+    if (bpsc == 1) return re > 0.0f;
+    if (bpsc == 2) return 2u * (im > 0.0f) + (re > 0.0f);
+    const float are = fabsf(re), aim = fabsf(im);
+    if (bpsc == 4) {
+        const float l = 0.6324555320336759f;
+        return (unsigned)(re > 0.0f) | (unsigned)(are < l) << 1 |
+               (unsigned)(im > 0.0f) << 2 | (unsigned)(aim < l) << 3;
+    }
+    const float l = 0.1543033499620919f;
+    const float l2 = 2.0f * l, l4 = 4.0f * l, l6 = 6.0f * l;
+    return (unsigned)(re > 0.0f) | (unsigned)(are < l4) << 1 |
+           (unsigned)(are < l6 && are > l2) << 2 |
+           (unsigned)(im > 0.0f) << 3 | (unsigned)(aim < l4) << 4 |
+           (unsigned)(aim < l6 && aim > l2) << 5;
+}
+
+/* num-complex's division: (a * conj(b)) / |b|^2, componentwise. */
+__device__ __forceinline__ float2 wlan_cdiv(float2 a, float2 b) {
+    const float n = b.x * b.x + b.y * b.y;
+    return make_float2((a.x * b.x + a.y * b.y) / n,
+                       (a.y * b.x - a.x * b.y) / n);
+}
+
+__device__ __forceinline__ float2 wlan_eq_lane(float2 v, int l) {
+    return make_float2(
+        __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.x), l)),
+        __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v.y), l)));
+}
+
+/* frame_equalizer.rs:241-246: training symbols, s11 - s25 + s39 + s53 */
+__device__ __forceinline__ float2 wlan_pilots_training(float2 s) {
+    const float2 a = wlan_eq_lane(s, 11), b = wlan_eq_lane(s, 25),
+                 c = wlan_eq_lane(s, 39), d = wlan_eq_lane(s, 53);
+    return make_float2(((a.x - b.x) + c.x) + d.x, ((a.y - b.y) + c.y) + d.y);
+}
+
+/* :249-254, :260-265: SIGNAL and data, p*s11 + p*s39 + p*s25 - p*s53 */
+__device__ __forceinline__ float2 wlan_pilots_data(float2 s, float p) {
+    const float2 a = wlan_eq_lane(s, 11), b = wlan_eq_lane(s, 39),
+                 c = wlan_eq_lane(s, 25), d = wlan_eq_lane(s, 53);
+    return make_float2(((a.x * p + b.x * p) + c.x * p) + d.x * -p,
+                       ((a.y * p + b.y * p) + c.y * p) + d.y * -p);
+}
+
+/* s * from_polar(1, -arg(sum)); the angle is wave-uniform */
+__device__ __forceinline__ float2 wlan_derotate(float2 s, float2 sum) {
+    const float beta = atan2f(sum.y, sum.x);
+    float sn, cs;
+    sincosf(-beta, &sn, &cs);
+    return make_float2(s.x * cs - s.y * sn, s.x * sn + s.y * cs);
+}
+
+__device__ __forceinline__ float wlan_wave_sum(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+struct WlanEqDesc {
+    unsigned long long sym_off, idx_off, eq_off;
+    unsigned n_avail, pad;
+};
+
+/* One wave per frame; frames strided over the grid's waves. Lane m loads
+ * FFT bin (m + 32) % 64 of the three leading symbols (:234-237), so the
+ * shift costs nothing. Writes h (64 values), snr and the 48 BPSK indices of
+ * the SIGNAL symbol to the workspace; a frame with fewer than 3 symbols
+ * gets indices 0 (its SIGNAL field is then decoded but never looked at),
+ * one with fewer than 2 also h = 0 and snr = 0. */
+__global__ __launch_bounds__(64 * WLAN_EQ_WAVES) void k_wlan_eq_head(
+    const float2* __restrict__ spec, const WlanEqDesc* __restrict__ frames,
+    int n_frames, float2* __restrict__ h_ws, float* __restrict__ snr_ws,
+    unsigned char* __restrict__ sig_ws) {
+    const unsigned lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned bin = (lane + 32) & 63;
+    const float lh = wlan_long_half(lane);
+    const int o = wlan_carrier_out(lane);
+
+    for (int f = (int)blockIdx.x * WLAN_EQ_WAVES + wave; f < n_frames;
+         f += (int)gridDim.x * WLAN_EQ_WAVES) {
+        const WlanEqDesc fr = frames[f];
+        const float2* s = spec + fr.sym_off;
+        float2 h = make_float2(0.0f, 0.0f);
+        float snr = 0.0f;
+        unsigned idx = 0;
+        if (fr.n_avail >= 2) {
+            float2 a = s[bin], b = s[64 + bin];
+            float2 c = make_float2(0.0f, 0.0f);
+            if (fr.n_avail >= 3) c = s[128 + bin];
+            a = wlan_derotate(a, wlan_pilots_training(a));
+            b = wlan_derotate(b, wlan_pilots_training(b));
+            /* sync2, :31-46 */
+            float nz = 0.0f, sg = 0.0f;
+            h = a;
+            if (lh != 0.0f) {
+                const float2 d = make_float2(a.x - b.x, a.y - b.y);
+                const float2 e = make_float2(a.x + b.x, a.y + b.y);
+                nz = d.x * d.x + d.y * d.y;
+                sg = e.x * e.x + e.y * e.y;
+                h = make_float2(e.x * lh, e.y * lh);
+            }
+            nz = wlan_wave_sum(nz);
+            sg = wlan_wave_sum(sg);
+            snr = 10.0f * log10f(sg / nz / 2.0f);
+            if (fr.n_avail >= 3) {
+                c = wlan_derotate(c, wlan_pilots_data(c, wlan_polarity(0)));
+                const float2 z = wlan_cdiv(c, h);
+                idx = wlan_demap(1, z.x, z.y);
+            }
+        }
+        h_ws[(size_t)f * 64 + lane] = h;
+        if (lane == 0) snr_ws[f] = snr;
+        if (o >= 0) sig_ws[(size_t)f * 48 + o] = (unsigned char)idx;
+    }
+}
+
+/* A frame is shared by `fblocks` consecutive blocks of the 1-D grid, so
+ * that the blocks running side by side read one contiguous stretch of the
+ * spectra; (frame, block of the frame) pairs are strided over the grid and
+ * a frame's data symbols over its fblocks * WLAN_EQ_WAVES waves. Every
+ * wave parses its frame's three raw SIGNAL bytes (wave-uniform; MSB =
+ * earlier bit) and leaves unless the field was found and it has a symbol
+ * below n_copied; h is loaded once per wave. The frame's first wave writes the info record, found or not. */
+__global__ __launch_bounds__(64 * WLAN_EQ_WAVES) void k_wlan_eq_data(
+    const float2* __restrict__ spec, const WlanEqDesc* __restrict__ frames,
+    int n_frames, const float2* __restrict__ h_ws,
+    const float* __restrict__ snr_ws, const unsigned* __restrict__ dec_ws,
+    unsigned char* __restrict__ idx, float2* __restrict__ eq,
+    fsdr_wlan_eq_info* __restrict__ info, unsigned fblocks) {
+    const unsigned lane = threadIdx.x & 63;
+    const unsigned wave =
+        (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const unsigned bin = (lane + 32) & 63;
+    const int o = wlan_carrier_out(lane);
+    const unsigned stride = fblocks * WLAN_EQ_WAVES;
+    const long long total = (long long)n_frames * fblocks;
+
+    for (long long vb = blockIdx.x; vb < total; vb += gridDim.x) {
+        const int f = (int)(vb / fblocks);
+        const unsigned slot0 =
+            (unsigned)(vb - (long long)f * fblocks) * WLAN_EQ_WAVES + wave;
+        const WlanEqDesc fr = frames[f];
+        const unsigned have = fr.n_avail >= 3 ? fr.n_avail - 3 : 0;
+        if (slot0 != 0 && slot0 >= have) continue;
+        unsigned mcs = 0, psdu = 0, n_sym = 0;
+        bool found = false;
+        if (fr.n_avail >= 3) {
+            const unsigned w = dec_ws[f]; /* bytes 0..2, little endian */
+            const unsigned bits = (__brev(w & 0xffu) >> 24) |
+                                  (__brev(w & 0xff00u) >> 8) |
+                                  (__brev(w & 0xff0000u) << 8);
+            found = wlan_signal_parse(bits, &mcs, &psdu);
+        }
+        if (found) n_sym = wlan_n_symbols(mcs, psdu);
+        const unsigned n_copied = min(n_sym, have);
+        if (slot0 == 0 && lane == 0) {
+            fsdr_wlan_eq_info r;
+            r.found = found;
+            r.mcs = found ? mcs : 0;
+            r.psdu_size = found ? psdu : 0;
+            r.n_symbols = n_sym;
+            r.n_copied = n_copied;
+            r.snr_db = snr_ws[f];
+            info[f] = r;
+        }
+        if (slot0 >= n_copied) continue;
+        const unsigned bpsc = wlan_n_bpsc(mcs);
+        const float2 h = h_ws[(size_t)f * 64 + lane];
+        const float2* s = spec + fr.sym_off + 3 * 64;
+        float2 next = s[(size_t)slot0 * 64 + bin];
+        for (unsigned slot = slot0; slot < n_copied; slot += stride) {
+            float2 v = next; /* the next symbol is loaded before this one's
+                                arithmetic */
+            if (slot + stride < n_copied)
+                next = s[(size_t)(slot + stride) * 64 + bin];
+            v = wlan_derotate(v, wlan_pilots_data(v, wlan_polarity(slot + 1)));
+            const float2 z = wlan_cdiv(v, h);
+            if (o >= 0) {
+                const size_t at = (size_t)slot * 48 + (unsigned)o;
+                idx[fr.idx_off + at] =
+                    (unsigned char)wlan_demap(bpsc, z.x, z.y);
+                if (eq) eq[fr.eq_off + at] = z;
+            }
+        }
+    }
+}
+
+/* ---- WLAN frame equalizer: host-only helpers and the handle ------------ */
+
+extern "C" int fsdr_wlan_demap(unsigned mcs, const fsdr_cf32* z, size_t n,
+                               uint8_t* out) {
+    if (!wlan_mcs_ok(mcs)) return FSDR_ERR_INVALID;
+    if (n && (!z || !out)) {
+        set_err("wlan: null argument");
+        return FSDR_ERR_INVALID;
+    }
+    const unsigned bpsc = wlan_n_bpsc(mcs);
+    for (size_t i = 0; i < n; i++)
+        out[i] = (uint8_t)wlan_demap(bpsc, z[i].re, z[i].im);
+    return FSDR_OK;
+}
+
+extern "C" int fsdr_wlan_pilot_polarity(size_t first, size_t count,
+                                        int8_t* out) {
+    if (count && !out) {
+        set_err("wlan: null argument");
+        return FSDR_ERR_INVALID;
+    }
+    for (size_t i = 0; i < count; i++)
+        out[i] = (int8_t)wlan_polarity((unsigned)((first + i) % 127));
+    return FSDR_OK;
+}
+
+extern "C" int fsdr_wlan_carrier_map(int8_t out[64]) {
+    if (!out) {
+        set_err("wlan: null argument");
+        return FSDR_ERR_INVALID;
+    }
+    for (unsigned m = 0; m < 64; m++) out[m] = (int8_t)wlan_carrier_out(m);
+    return FSDR_OK;
+}
+
+struct fsdr_wlan_equalizer {
+    fsdr_wlan_decoder* dec = nullptr; /* the SIGNAL fields' own decoder */
+    dev_buf desc;                     /* the frame descriptors */
+    /* per frame: h (64 cf32), snr, 48 SIGNAL indices, and the SIGNAL
+     * decode's 3 raw bytes (one word), 2 out bytes and crc byte */
+    dev_buf ws_h, ws_snr, ws_sig, ws_dec, ws_out, ws_crc;
+    WlanEqDesc* pinned = nullptr;
+    size_t pinned_cap = 0;
+    hipEvent_t uploaded = nullptr;
+    /* staging of fsdr_wlan_equalize_host */
+    dev_buf st_spec, st_idx, st_eq, st_info;
+    ~fsdr_wlan_equalizer() {
+        if (uploaded) {
+            (void)hipEventSynchronize(uploaded);
+            (void)hipEventDestroy(uploaded);
+        }
+        if (pinned) (void)hipHostFree(pinned);
+        delete dec;
+    }
+};
+
+extern "C" fsdr_wlan_equalizer* fsdr_wlan_equalizer_create(void) {
+    fsdr_wlan_equalizer* eq = new fsdr_wlan_equalizer();
+    eq->dec = fsdr_wlan_decoder_create(); /* buffers come with the first call */
+    return eq;
+}
+
+extern "C" void fsdr_wlan_equalizer_destroy(fsdr_wlan_equalizer* eq) {
+    delete eq;
+}
+
+static unsigned wlan_eq_slots(const fsdr_wlan_eq_frame& f) {
+    return f.n_avail >= 3 ? f.n_avail - 3 : 0;
+}
+
+static int wlan_eq_check(const fsdr_wlan_equalizer* eq,
+                         const fsdr_wlan_eq_frame* frames, size_t n_frames) {
+    if (!eq) {
+        set_err("wlan: null equalizer");
+        return FSDR_ERR_INVALID;
+    }
+    if (n_frames && !frames) {
+        set_err("wlan: null frame array");
+        return FSDR_ERR_INVALID;
+    }
+    if (n_frames > (size_t)1 << 30) {
+        set_err("wlan: too many frames");
+        return FSDR_ERR_INVALID;
+    }
+    return FSDR_OK;
+}
+
+static int wlan_eq_launch(fsdr_wlan_equalizer* eq, const void* d_spec,
+                          const fsdr_wlan_eq_frame* frames, size_t n_frames,
+                          void* d_idx, void* d_eq, void* d_info,
+                          hipStream_t st) {
+    if (!eq->uploaded)
+        HIP_TRY(hipEventCreateWithFlags(&eq->uploaded,
+                                        hipEventDisableTiming));
+    /* the previous call's copy may still be reading the pinned image */
+    HIP_TRY(hipEventSynchronize(eq->uploaded));
+    if (eq->pinned_cap < n_frames) {
+        if (eq->pinned) HIP_TRY(hipHostFree(eq->pinned));
+        eq->pinned = nullptr;
+        eq->pinned_cap = 0;
+        HIP_TRY(hipHostMalloc((void**)&eq->pinned,
+                              n_frames * sizeof(WlanEqDesc)));
+        eq->pinned_cap = n_frames;
+    }
+    unsigned max_slots = 1; /* every frame needs the wave of slot 0 */
+    std::vector<fsdr_wlan_frame> sig(n_frames);
+    for (size_t i = 0; i < n_frames; i++) {
+        const fsdr_wlan_eq_frame& f = frames[i];
+        WlanEqDesc& d = eq->pinned[i];
+        d.sym_off = f.sym_off;
+        d.idx_off = f.idx_off;
+        d.eq_off = f.eq_off;
+        d.n_avail = f.n_avail;
+        d.pad = 0;
+        max_slots = std::max(
+            max_slots, std::min<unsigned>(wlan_eq_slots(f), WLAN_EQ_MAX_SYM));
+        sig[i].mcs = 0;
+        sig[i].psdu_size = 0;
+        sig[i].sym_off = 48 * i;
+        sig[i].out_off = 2 * i;
+        sig[i].dec_off = 4 * i;
+    }
+    HIP_TRY(eq->desc.ensure(n_frames * sizeof(WlanEqDesc)));
+    HIP_TRY(eq->ws_h.ensure(n_frames * 64 * sizeof(float2)));
+    HIP_TRY(eq->ws_snr.ensure(n_frames * sizeof(float)));
+    HIP_TRY(eq->ws_sig.ensure(n_frames * 48));
+    HIP_TRY(eq->ws_dec.ensure(n_frames * 4));
+    HIP_TRY(eq->ws_out.ensure(n_frames * 2));
+    HIP_TRY(eq->ws_crc.ensure(n_frames));
+    HIP_TRY(hipMemcpyAsync(eq->desc.ptr, eq->pinned,
+                           n_frames * sizeof(WlanEqDesc),
+                           hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(eq->uploaded, st));
+
+    const long long hblocks =
+        ((long long)n_frames + WLAN_EQ_WAVES - 1) / WLAN_EQ_WAVES;
+    const int hgrid = (int)std::min<long long>(hblocks, grid_cap(256 * 8));
+    hipLaunchKernelGGL(k_wlan_eq_head, dim3(hgrid), dim3(64 * WLAN_EQ_WAVES),
+                       0, st, (const float2*)d_spec,
+                       eq->desc.as<const WlanEqDesc>(), (int)n_frames,
+                       eq->ws_h.as<float2>(), eq->ws_snr.as<float>(),
+                       eq->ws_sig.as<unsigned char>());
+    HIP_TRY(hipGetLastError());
+
+    int rc = fsdr_wlan_decode_dev(eq->dec, eq->ws_sig.ptr, sig.data(),
+                                  n_frames, eq->ws_out.ptr, eq->ws_dec.ptr,
+                                  eq->ws_crc.ptr, st);
+    if (rc) return rc;
+
+    const unsigned fblocks = std::min<unsigned>(
+        (max_slots + WLAN_EQ_WAVES - 1) / WLAN_EQ_WAVES, WLAN_EQ_SLOT_BLOCKS);
+    const int dgrid = (int)std::min<long long>(
+        (long long)n_frames * fblocks, grid_cap(1 << 20));
+    hipLaunchKernelGGL(k_wlan_eq_data, dim3(dgrid),
+                       dim3(64 * WLAN_EQ_WAVES), 0, st,
+                       (const float2*)d_spec, eq->desc.as<const WlanEqDesc>(),
+                       (int)n_frames, eq->ws_h.as<const float2>(),
+                       eq->ws_snr.as<const float>(),
+                       eq->ws_dec.as<const unsigned>(),
+                       (unsigned char*)d_idx, (float2*)d_eq,
+                       (fsdr_wlan_eq_info*)d_info, fblocks);
+    HIP_TRY(hipGetLastError());
+    return FSDR_OK;
+}
+
+extern "C" int fsdr_wlan_equalize_dev(fsdr_wlan_equalizer* eq,
+                                      const void* d_spec,
+                                      const fsdr_wlan_eq_frame* frames,
+                                      size_t n_frames, void* d_idx,
+                                      void* d_eq, void* d_info,
+                                      void* stream) {
+    int rc = wlan_eq_check(eq, frames, n_frames);
+    if (rc) return rc;
+    if (n_frames == 0) return FSDR_OK;
+    if (!d_spec || !d_idx || !d_info) {
+        set_err("wlan: null device pointer");
+        return FSDR_ERR_INVALID;
+    }
+    REQUIRE_GPU();
+    return wlan_eq_launch(eq, d_spec, frames, n_frames, d_idx, d_eq, d_info,
+                          (hipStream_t)stream);
+}
+
+extern "C" int fsdr_wlan_equalize_host(fsdr_wlan_equalizer* eq,
+                                       const fsdr_cf32* spec,
+                                       const fsdr_wlan_eq_frame* frames,
+                                       size_t n_frames, uint8_t* idx,
+                                       fsdr_cf32* eq_syms,
+                                       fsdr_wlan_eq_info* info) {
+    int rc = wlan_eq_check(eq, frames, n_frames);
+    if (rc) return rc;
+    if (n_frames == 0) return FSDR_OK;
+    if (!spec || !idx || !info) {
+        set_err("wlan: null argument");
+        return FSDR_ERR_INVALID;
+    }
+    REQUIRE_GPU();
+    size_t ss = 1, is = 1, es = 1;
+    for (size_t i = 0; i < n_frames; i++) {
+        const fsdr_wlan_eq_frame& f = frames[i];
+        const size_t out = 48 * (size_t)wlan_eq_slots(f);
+        ss = std::max(ss, f.sym_off + 64 * (size_t)f.n_avail);
+        is = std::max(is, f.idx_off + out);
+        es = std::max(es, f.eq_off + out);
+    }
+    HIP_TRY(eq->st_spec.ensure(ss * sizeof(float2)));
+    HIP_TRY(eq->st_idx.ensure(is));
+    HIP_TRY(eq->st_info.ensure(n_frames * sizeof(fsdr_wlan_eq_info)));
+    if (eq_syms) HIP_TRY(eq->st_eq.ensure(es * sizeof(float2)));
+    HIP_TRY(hipMemcpy(eq->st_spec.ptr, spec, ss * sizeof(float2),
+                      hipMemcpyHostToDevice));
+    rc = wlan_eq_launch(eq, eq->st_spec.ptr, frames, n_frames,
+                        eq->st_idx.ptr, eq_syms ? eq->st_eq.ptr : nullptr,
+                        eq->st_info.ptr, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpy(info, eq->st_info.ptr,
+                      n_frames * sizeof(fsdr_wlan_eq_info),
+                      hipMemcpyDeviceToHost));
+    /* only what the frames' info records say was written reaches the
+     * caller's spans */
+    std::vector<uint8_t> hi(is);
+    HIP_TRY(hipMemcpy(hi.data(), eq->st_idx.ptr, is, hipMemcpyDeviceToHost));
+    std::vector<fsdr_cf32> he;
+    if (eq_syms) {
+        he.resize(es);
+        HIP_TRY(hipMemcpy(he.data(), eq->st_eq.ptr, es * sizeof(float2),
+                          hipMemcpyDeviceToHost));
+    }
+    for (size_t i = 0; i < n_frames; i++) {
+        const size_t n = 48 * (size_t)info[i].n_copied;
+        memcpy(idx + frames[i].idx_off, hi.data() + frames[i].idx_off, n);
+        if (eq_syms)
+            memcpy(eq_syms + frames[i].eq_off, he.data() + frames[i].eq_off,
+                   n * sizeof(fsdr_cf32));
+    }
     return FSDR_OK;
 }
 

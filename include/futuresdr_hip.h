@@ -620,6 +620,80 @@ int fsdr_wlan_depuncture_map(unsigned mcs, size_t n_symbols, size_t first,
 int fsdr_wlan_signal_field(const uint8_t* bits24, int* found, unsigned* mcs,
                            size_t* psdu_size);
 
+/* WLAN frame equalizer — examples/wlan FrameEqualizer (src/
+ * frame_equalizer.rs) for a batch of frames, lane = carrier. The reference
+ * is a stream state machine driven by "wifi_start" tags; here the caller
+ * says where each frame's symbols start and how many there are, and the
+ * frames of a batch are independent.
+ * Input: the plain forward 64-point FFT (no shift, no scaling) of
+ * fsdr_wlan_sync_long_run's stream; per frame two long-training symbols,
+ * the SIGNAL symbol, then data symbols. Carrier m is FFT bin (m + 32) % 64
+ * (:234-237).
+ * Every symbol (:239-271) is multiplied by (cos(-beta), sin(-beta)), beta =
+ * arg of its pilot sum over carriers 11, 25, 39, 53: s11 - s25 + s39 + s53
+ * for the training symbols, p*s11 + p*s39 + p*s25 - p*s53 otherwise, with
+ * p = POLARITY[0] for SIGNAL and POLARITY[(j + 1) % 127] for data symbol j
+ * (lib.rs:365, the x^7+x^4+1 scrambler seeded with ones, as +1 / -1).
+ * Channel (:27-46): h = first training symbol; the second, s, gives on
+ * carriers 6..58 except 32 noise += |h-s|^2, signal += |h+s|^2 and
+ * h = (h+s) / (2*LONG[m]) (lib.rs:495); snr_db = 10*log10(signal/noise/2).
+ * Equalize (:48-62): the 48 data carriers (6..58 without 11, 25, 32, 39,
+ * 53) in ascending order, z = s/h by num-complex's division, index =
+ * Modulation::demap(z) (lib.rs:177-218, strict comparisons, f32 thresholds;
+ * NaN gives 0).
+ * SIGNAL (:294-331, :121-175): equalized as BPSK, decoded as a frame of
+ * (mcs 0, psdu 0) by the decoder above, first 24 decoded bits parsed by the
+ * rule of fsdr_wlan_signal_field. No parse: found = 0 and nothing else of
+ * the frame is written. A parse gives mcs, psdu_size (any length up to
+ * 4095) and n_symbols (FrameParam::new); n_copied = min(n_symbols,
+ * n_avail - 3) data symbols are equalized with that modulation.
+ * Sums over carriers are formed in a different order than the reference's
+ * loop, and atan2f/sincosf are the device's: results agree with the
+ * reference's f32 arithmetic to rounding, not bit for bit.
+ * _create/_destroy: the handle owns its workspace (h, snr, the SIGNAL
+ *   indices and decode), a private decoder and the staging of _host.
+ *   Creating needs no device. One handle serves one stream at a time.
+ * _equalize_dev: `frames` is a host array, free for reuse on return. Frame
+ *   i reads 64*n_avail cf32 at d_spec + sym_off and writes 48*n_copied
+ *   index bytes at d_idx + idx_off, if d_eq is not NULL as many equalized
+ *   cf32 values (the reference's `symbols` message) at d_eq + eq_off, and
+ *   d_info[i] (always: all zeros except snr_db when not found; snr_db = 0
+ *   when n_avail < 2). Nothing else is written; output ranges must not
+ *   overlap (not checked). Three launches on `stream`, no host
+ *   synchronisation. FSDR_ERR_INVALID plus an error string, and no launch,
+ *   for a NULL pointer other than d_eq; n_frames == 0 is a successful
+ *   no-op. Validation precedes the device check.
+ * _equalize_host: the same over host spans, synchronous.
+ * Host-only: _demap is the kernel's demap for mcs 0..7 on n values.
+ *   _pilot_polarity: POLARITY[(first + i) % 127], i < count, as +1 / -1.
+ *   _carrier_map: output position of carrier m, -1 for pilot, DC, guard. */
+typedef struct fsdr_wlan_equalizer fsdr_wlan_equalizer;
+typedef struct {
+    size_t   sym_off; /* cf32 items into d_spec */
+    uint32_t n_avail; /* 64-item symbols from sym_off, training and SIGNAL
+                         included */
+    size_t   idx_off; /* bytes into d_idx; room for 48*(n_avail-3), 0 if
+                         n_avail < 3 */
+    size_t   eq_off;  /* cf32 items into d_eq; unused if d_eq is NULL */
+} fsdr_wlan_eq_frame;
+typedef struct {
+    uint32_t found, mcs, psdu_size, n_symbols, n_copied;
+    float    snr_db;
+} fsdr_wlan_eq_info;
+fsdr_wlan_equalizer* fsdr_wlan_equalizer_create(void);
+void fsdr_wlan_equalizer_destroy(fsdr_wlan_equalizer* eq);
+int fsdr_wlan_equalize_dev(fsdr_wlan_equalizer* eq, const void* d_spec,
+                           const fsdr_wlan_eq_frame* frames, size_t n_frames,
+                           void* d_idx, void* d_eq, void* d_info,
+                           void* stream);
+int fsdr_wlan_equalize_host(fsdr_wlan_equalizer* eq, const fsdr_cf32* spec,
+                            const fsdr_wlan_eq_frame* frames, size_t n_frames,
+                            uint8_t* idx, fsdr_cf32* eq_syms,
+                            fsdr_wlan_eq_info* info);
+int fsdr_wlan_demap(unsigned mcs, const fsdr_cf32* z, size_t n, uint8_t* out);
+int fsdr_wlan_pilot_polarity(size_t first, size_t count, int8_t* out);
+int fsdr_wlan_carrier_map(int8_t out[64]);
+
 /* MFMA-loop microbenchmark (diagnostics; tools/mfma_ubench.py): times
  * the chain kernel's inner MFMA loop on LDS staged once. */
 int fsdr_mfma_ubench(int grid, int iters, double* tflops, void* stream);

@@ -6,7 +6,8 @@ staged path per shape, plus the channelizer at the same shape for
 context). Prints TF/s or GB/s vs peak. --synth runs the PFB synthesizer
 part only, --arb the PFB arbitrary-rate resampler part only, --iir the IIR
 filter part only, --lora the LoRa FFT demodulator part only, --wlan-decode
-the WLAN frame decoder part only."""
+the WLAN frame decoder part only, --wlan-eq the WLAN frame equalizer part
+only."""
 import ctypes
 import os
 import sys
@@ -316,10 +317,99 @@ def wlan_decode_lines(lib, st, rounds=5):
         run(0, 100, 1 << k)
 
 
+def wlan_eq_frame(mcs, psdu, n_data, rng):
+    """Spectra (FFT-bin order, cf32) of one frame with n_data data symbols
+    behind a flat unit channel: the long-training sequence twice, the SIGNAL
+    symbol for (mcs, psdu), then pilots of the right polarity and uniformly
+    random values on the data carriers (the kernel's work does not depend
+    on them)."""
+    cm = fa.wlan_carrier_map()
+    data = cm >= 0
+    long_seq = np.zeros(64)
+    long_seq[6:59] = [{"+": 1.0, "-": -1.0, "0": 0.0}[c] for c in
+                      "++--++-+-++++++--++-+-++++0+--++-+-+-----++--+-+-++++"]
+    rate = {0: 11, 1: 15, 2: 10, 3: 14, 4: 9, 5: 13, 6: 8, 7: 12}[mcs]
+    bits = np.zeros(24, np.int64)
+    bits[:4] = (rate >> np.arange(4)) & 1
+    bits[5:17] = (psdu >> np.arange(12)) & 1
+    bits[17] = bits[:17].sum() & 1
+    coded, state = np.zeros(48, np.int64), 0
+    for i, b in enumerate(bits):
+        state = ((state << 1) & 0x7E) | int(b)
+        coded[2 * i] = bin(state & 0o155).count("1") & 1
+        coded[2 * i + 1] = bin(state & 0o117).count("1") & 1
+    sig = np.zeros(48, np.int64)
+    i = np.arange(48)
+    sig[3 * (i % 16) + i // 16] = coded
+    pol = fa.wlan_pilot_polarity(n_data + 1).astype(np.float64)
+    rows = np.zeros((3 + n_data, 64), np.complex128)
+    rows[0] = rows[1] = long_seq
+    rows[2:, [11, 25, 39]] = pol[:, None]
+    rows[2:, 53] = -pol
+    rows[2, data] = 2.0 * sig[cm[data]] - 1.0
+    rows[3:, data] = rng.uniform(-1, 1, (n_data, 48)) \
+        + 1j * rng.uniform(-1, 1, (n_data, 48))
+    return np.roll(rows, 32, axis=1).astype(np.complex64).reshape(-1)
+
+
+def wlan_eq_lines(lib, st, rounds=5):
+    """WLAN frame equalizer over device-resident batches of equal frames:
+    Bpsk_1_2 and Qam64_3_4 at 4 data symbols and at the longest frame below
+    250 data symbols that the SIGNAL field can announce (250 at Bpsk_1_2;
+    152 at Qam64_3_4, psdu 4095), 16384 frames and a single frame. One timing
+    is one fsdr_wlan_equalize_dev call between two events (both descriptor
+    uploads, k_wlan_eq_head, the SIGNAL decode and k_wlan_eq_data; d_eq
+    NULL); 2 warm-up calls, then `rounds` timings; median and range, and the
+    share of the HBM floor of 560 B per data symbol (512 in, 48 out) at
+    PEAK_HBM."""
+    eq = fa.WlanEqualizer()
+    rng = np.random.default_rng(12)
+
+    def run(mcs, n_data, batch):
+        psdu = max(p for p in range(4096)
+                   if fa.wlan_frame_param(mcs, p)[0] == n_data)
+        frame = wlan_eq_frame(mcs, psdu, n_data, rng)
+        spec = torch.from_numpy(frame).cuda().repeat(batch)
+        idx = torch.empty(batch * 48 * n_data, dtype=torch.uint8,
+                          device="cuda")
+        info = torch.zeros(batch * 24, dtype=torch.uint8, device="cuda")
+        descs = eq._descs([(i * frame.size, 3 + n_data, i * 48 * n_data, 0)
+                           for i in range(batch)])
+
+        def call():
+            rc = lib.fsdr_wlan_equalize_dev(eq._h, spec.data_ptr(), descs,
+                                            batch, idx.data_ptr(), None,
+                                            info.data_ptr(), st.cuda_stream)
+            assert rc == 0, lib.fsdr_last_error()
+
+        v = sorted(timeit(call, reps=1, warm=2) for _ in range(rounds))
+        rec = info.cpu().numpy().view(fa.WLAN_EQ_INFO_DTYPE)
+        assert (rec["found"] == 1).all() and (rec["mcs"] == mcs).all() and \
+            (rec["psdu_size"] == psdu).all() and \
+            (rec["n_copied"] == n_data).all(), rec[:2]
+        med = v[len(v) // 2]
+        floor = batch * n_data * 560 / (med * 1e-3) / 1e12
+        name = {0: "Bpsk_1_2", 7: "Qam64_3_4"}[mcs]
+        print(f"{name:9s} {n_data:3d} data symbols (psdu {psdu:4d}) x "
+              f"{batch:5d}: {med:8.3f} ms median of {rounds} "
+              f"[{v[0]:.3f}..{v[-1]:.3f}]  "
+              f"{batch * n_data / med / 1e3:8.2f} M symbols/s  "
+              f"{floor:6.3f} TB/s = {100 * floor / PEAK_HBM:5.1f} % of the "
+              f"HBM floor")
+
+    for mcs, long_n in ((0, 250), (7, 152)):
+        for n_data in (4, long_n):
+            for batch in (1, 16384):
+                run(mcs, n_data, batch)
+
+
 def main():
     lib = fa.lib()
     fa.set_device(0)
     st = torch.cuda.current_stream()
+    if "--wlan-eq" in sys.argv[1:]:
+        wlan_eq_lines(lib, st)
+        return
     if "--wlan-decode" in sys.argv[1:]:
         wlan_decode_lines(lib, st)
         return
